@@ -16,6 +16,10 @@ over the ranks (contiguous blocks, global trajectory numbering, so every rank co
 exchange while stepping; one RCCL all-gather of the final posterior means at the end of each pass, inside the timed
 region.  With more than one rank the line also carries a `weak_scaling` object: the same loop with 65 536
 trajectories PER GPU (`--mode weak` makes that the headline instead).
+
+`--dump-outputs DIR` writes what the last timed pass computed as float64 .npy files (<= 64 MB): the records of a fixed,
+seeded sample of trajectories and the final means, log-likelihoods and retcodes, so two builds can be compared output for
+output (write_dump lists the arrays).
 """
 import argparse
 import json
@@ -30,6 +34,46 @@ sys.path.insert(0, ROOT)
 
 B_ALG_STEP = lambda D: 8 * (D + D * (D + 1) // 2 + 1)  # bytes written per trajectory-step
 HBM_PEAK = 8.0e12  # B/s, MI355X_MICROARCH.md (spec; 6.29e12 measured streaming copy)
+DUMP_SEED = 0x0DEF0D0F  # --dump-outputs: the trajectory / record sample is a pure function of the arguments
+DUMP_BYTES = 64 << 20  # --dump-outputs: cap on everything written
+DUMP_RECORD_BYTES = 48 << 20  # of which the per-record sample (mean, covariance, diffusion) may take this much
+DUMP_TRAJ = 64  # trajectories whose records are dumped
+DUMP_FINAL_TRAJ = 1 << 16  # trajectories whose final mean / log-likelihood / retcode are dumped
+
+
+def dump_plan(total_traj, n_save, D, TRI):
+    """Global trajectory indices and record slots of the --dump-outputs sample (sorted, seeded, rank-count independent)."""
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def pick(n, k):
+        return np.arange(n) if n <= k else np.sort(rng.choice(n, size=k, replace=False))
+
+    traj = pick(total_traj, DUMP_TRAJ)
+    r_max = max(2, DUMP_RECORD_BYTES // (len(traj) * (D + TRI + 1) * 8))
+    rec = np.arange(n_save) if n_save <= r_max else np.unique(np.r_[0, pick(n_save, r_max - 2), n_save - 1])
+    final = pick(total_traj, DUMP_FINAL_TRAJ)
+    return traj, rec, final
+
+
+def write_dump(out_dir, plan, parts):
+    """Writes the per-rank parts (rank order = global trajectory order) of the --dump-outputs sample as float64 .npy:
+    mean [traj, record, D], cov_tril [traj, record, TRI] and diffusion [traj, record] of the sampled trajectories at the
+    sampled record slots; mean_final [traj, D], loglik and retcode of the final-record sample; the sample indices."""
+    traj, rec, fin = plan
+    cat = lambda k: np.concatenate([p[k] for p in parts], axis=0)
+    assert np.array_equal(cat("traj"), traj) and np.array_equal(cat("final"), fin), "dump sample incomplete"
+    arrays = {
+        "mean": cat("mean"), "cov_tril": cat("cov_tril"), "diffusion": cat("diffusion"),
+        "mean_final": cat("mean_final"), "loglik": cat("loglik"), "retcode": cat("retcode"),
+        "sample_trajectories": traj, "sample_records": rec, "sample_final_trajectories": fin,
+    }
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "bytes": total, "seed": DUMP_SEED, "arrays": {k: list(a.shape) for k, a in arrays.items()}}
 
 
 def cpu_baseline(seconds_budget=15.0):
@@ -76,7 +120,11 @@ def main():
     ap.add_argument("--save", choices=["everystep", "final"], default="everystep")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-smoother", action="store_true", help="skip the RTS smoother pass measured after the timed loop")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed pass computed (a fixed, seeded sample; float64 .npy, <= 64 MB) to DIR")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     import torch
 
@@ -99,9 +147,10 @@ def main():
     tgrid = np.arange(nsteps + 1) * dt
     stream = torch.cuda.current_stream(dev)
 
-    def run(mode, steps, warmup, with_smoother=False):
+    def run(mode, steps, warmup, with_smoother=False, plan=None):
         """One timed loop.  Returns (seconds for `steps` passes [max over ranks], kernel ms, N per rank, parity info, ...).
-        with_smoother: after the timed loop (outside it) the RTS smoother runs over the records of the last pass."""
+        with_smoother: after the timed loop (outside it) the RTS smoother runs over the records of the last pass.
+        plan: dump_plan(...) of --dump-outputs; this rank's part of that sample of the last pass is returned last."""
         if mode == "strong":
             lo, hi = od.shard_bounds(args.total_traj, rank, world)
             N, first = hi - lo, lo
@@ -154,6 +203,25 @@ def main():
             t = torch.tensor([el], dtype=torch.float64, device=dev)
             torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
             el = float(t.item())
+        dumped = None
+        if plan is not None:  # taken before the parity check and the smoother touch anything: the last timed pass as it left it
+            from odefilters_jl_amd.host import F_DIFFUSION, F_LOGLIK, F_RETCODE
+
+            traj, rec, fin = plan
+            t_own = traj[(traj >= first) & (traj < first + N)]
+            f_own = fin[(fin >= first) & (fin < first + N)]
+            ti = torch.as_tensor(t_own - first, device=dev)
+            ri = torch.as_tensor(rec, device=dev)
+            fi = torch.as_tensor(f_own - first, device=dev)
+            records = lambda buf: buf.index_select(2, ti).index_select(0, ri).permute(2, 0, 1).cpu().numpy()  # [traj, record, :]
+            dumped = {
+                "traj": t_own, "final": f_own,
+                "mean": records(mean), "cov_tril": records(cov),
+                "diffusion": ctx.get(F_DIFFUSION)[rec][:, t_own - first].T,
+                "mean_final": mean[n_save - 1].index_select(1, fi).T.cpu().numpy(),
+                "loglik": ctx.get(F_LOGLIK)[f_own - first],
+                "retcode": ctx.get(F_RETCODE)[f_own - first].astype(np.float64),
+            }
         finite_ok = bool(torch.isfinite(final).all().item()) and bool((ctx.get(10) == 0).all())
         # parity inside the bench: THIS run's records against the committed oracle fixture (tests/golden/full_lorenz_fixed.npz: the
         # same ensemble, 1 024 steps; seven trajectories at seven record times 0 ... 1 024) -- solution means of the seven records
@@ -213,10 +281,20 @@ def main():
         ctx.close()
         del mean, cov, smean, scov
         torch.cuda.empty_cache()
-        return el, k_ms, N, finite_ok, parity, kname, smoother
+        return el, k_ms, N, finite_ok, parity, kname, smoother, dumped
 
-    el, k_ms, N, finite_ok, parity, kname, smoother = run(args.mode, args.steps, args.warmup, with_smoother=not args.no_smoother)
-    total_traj = args.total_traj if args.mode == "strong" else world * N
+    total_traj = args.total_traj if args.mode == "strong" else world * args.traj
+    plan = dump_plan(total_traj, n_save, D, TRI) if args.dump_outputs else None
+    el, k_ms, N, finite_ok, parity, kname, smoother, dumped = run(args.mode, args.steps, args.warmup,
+                                                                 with_smoother=not args.no_smoother, plan=plan)
+    dump_info = None
+    if plan is not None:
+        parts = [dumped]
+        if world > 1:
+            parts = [None] * world if rank == 0 else None
+            torch.distributed.gather_object(dumped, parts, dst=0)
+        if rank == 0:
+            dump_info = write_dump(args.dump_outputs, plan, parts)
     value = total_traj * nsteps * args.steps / el
     alg_bytes = B_ALG_STEP(D) * N * (nsteps + 1 if everystep else 1)
     achieved = alg_bytes / (k_ms * 1e-3)
@@ -234,7 +312,7 @@ def main():
     other = None
     if world > 1:  # the other scaling mode beside the headline
         om = "weak" if args.mode == "strong" else "strong"
-        el2, k2, N2, _, _, kname2, _ = run(om, max(2, args.steps // 2), 1)
+        el2, k2, N2, _, _, kname2, _, _ = run(om, max(2, args.steps // 2), 1)
         tot2 = args.total_traj if om == "strong" else world * N2
         other = {"scaling": om, "value": tot2 * nsteps * max(2, args.steps // 2) / el2, "unit": "filter steps/s",
                  "trajectories_per_gpu": N2, "ms_per_step": el2 / max(2, args.steps // 2) * 1e3, "kernel_ms": k2, "kernel": kname2}
@@ -273,6 +351,8 @@ def main():
         }
         if smoother:
             line["smoother"] = smoother
+        if dump_info:
+            line["dump_outputs"] = dump_info
         if other:
             line[other["scaling"] + "_scaling"] = other
         if world > 1:

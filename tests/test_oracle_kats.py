@@ -1,6 +1,6 @@
 """Pins the oracle (oracle/odefilter_oracle.py) to the reference's own tests.
 
-Each test restates one test of /root/reference/test (cited), on seeded random inputs where
+Each test restates one test of the reference's test/ directory (cited), on seeded random inputs where
 the reference uses bare `rand`.  CPU only.
 """
 import math
