@@ -64,9 +64,7 @@ struct odef_ctx {
   long n_save = 0;
   bool adaptive = false;
   bool solved = false;
-  bool team_path = false;   // workgroup-per-trajectory kernels (large state dimension)
-  const TeamLaunch* team = nullptr;  // ... and their launch functions for this vector field
-  JitModule* jit = nullptr; // run-time compiled vector field (rhs_id >= 100); owned by the registry in jit.hip
+  const FieldLaunch* field = nullptr;  // launch functions of the vector field (compiled-in, or owned by the registry in jit.hip)
   double* d_ws = nullptr;   // per-trajectory workspace of the team kernels
   double* d_stage = nullptr;  // trajectory-major stage of the covariance records (D = 168 smoother, record_stage.h)
   long stage_filter_recs = 0; // > 0: the last solve left this many filter records in the stage (record r at r N ld)
@@ -85,6 +83,9 @@ struct odef_ctx {
 };
 
 namespace {
+
+// the field runs on the workgroup-per-trajectory kernels (large state dimension)
+bool team_path(const odef_ctx* c) { return c->field->smooth_staged != nullptr; }
 
 int fail(odef_ctx* c, const char* fmt, ...) {
   char buf[512];
@@ -321,8 +322,7 @@ int odef_create(odef_ctx** out, const odef_config* cfg) {
     return fail(nullptr, "odef_create: unknown diffusion model %d", cfg->diffusion);
   if (cfg->n_traj <= 0) return fail(nullptr, "odef_create: n_traj must be positive");
   // run-time compiled fields: lane / row-team kernels up to state dimension 20 (d <= 10), the workgroup-per-trajectory kernels above
-  const bool jit_team = cfg->rhs_id >= kJitFirstId && (cfg->d * (cfg->order + 1) > 20 || cfg->d > 10);
-  if (jit_team && (cfg->d % 2 != 0 || cfg->d > 32 || cfg->d * (cfg->order + 1) > 176))
+  if (cfg->rhs_id >= kJitFirstId && jit_team_path(cfg->d, cfg->order) && (cfg->d % 2 != 0 || cfg->d > 32 || cfg->d * (cfg->order + 1) > 176))
     return fail(nullptr, "odef_create: run-time compiled vector fields above state dimension 20 run on the workgroup-per-trajectory kernels: even d <= 32 and d(q+1) <= 176 (got d = %d, d(q+1) = %d)",
                 cfg->d, cfg->d * (cfg->order + 1));
   int ndev = 0;
@@ -340,27 +340,17 @@ int odef_create(odef_ctx** out, const odef_config* cfg) {
   else if (hipGetDevice(&c->device) != hipSuccess) c->device = 0;
   if (c->device >= ndev) { delete c; return fail(nullptr, "odef_create: device %d not present (%d devices)", cfg->device, ndev); }
   build_prior(c->q, c->pc);
-  c->team = team_launch(cfg->rhs_id);
-  c->team_path = c->team != nullptr;
-  hipError_t e = hipSetDevice(c->device);
-  if (e == hipSuccess && jit_team) {
+  c->field = field_launch(cfg->rhs_id);
+  if (!c->field) {
     std::string jerr;
-    c->team = jit_get_team(cfg->rhs_id, c->q, cfg->alg == ODEF_EK1, team_abi_stamp(), jerr);
-    c->team_path = c->team != nullptr;
-    if (!c->team) {
+    c->field = jit_field(cfg->rhs_id, c->q, cfg->alg == ODEF_EK1, team_abi_stamp(), jerr);
+    if (!c->field) {
       g_create_error = "odef_create: " + jerr;  // the whole compiler log
       delete c;
       return -1;
     }
-  } else if (e == hipSuccess && cfg->rhs_id >= kJitFirstId) {
-    std::string jerr;
-    c->jit = jit_get_module(cfg->rhs_id, c->q, cfg->alg == ODEF_EK1, c->device, jerr);
-    if (!c->jit) {
-      fail(nullptr, "odef_create: %s", jerr.substr(0, 400).c_str());
-      delete c;
-      return -1;
-    }
   }
+  hipError_t e = hipSetDevice(c->device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking);
   for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreate(&c->ev[k]);
   const size_t N = (size_t)cfg->n_traj;
@@ -605,30 +595,19 @@ int odef_solve_fixed(odef_ctx* c, const double* tgrid, int64_t n_t) {
   P.tab_idx = c->d_tab_idx;
   P.nsteps = nsteps;
   P.t0 = c->t0;
-  int rc;
-  if (c->team_path) {
-    size_t have = 0;
+  size_t have = 0;
+  if (team_path(c)) {
     if (P.everystep) {  // the matrix-core kernel writes its records through the trajectory-major stage when all of them fit
       const size_t tri = (size_t)c->D * (c->D + 1) / 2, per_rec = (size_t)P.N * ((tri + 15) / 16 * 16);
       have = ensure_stage(c, nsteps + 1, per_rec);
       if (have < (size_t)(nsteps + 1) * per_rec) have = 0;
     }
-    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-    rc = c->team->filter(c->q, c->cfg.alg == ODEF_EK1, P, c->stream, 0, have ? c->d_stage : nullptr, have, &c->stage_filter_recs);
-  } else {
+  } else if ((size_t)c->TRI * (size_t)c->cfg.n_traj * sizeof(double) >= (1ull << 31)) {
     // one lane per trajectory: the per-field buffer descriptors carry 32-bit sizes
-    if ((size_t)c->TRI * (size_t)c->cfg.n_traj * sizeof(double) >= (1ull << 31))
-      return fail(c, "odef_solve_fixed: n_traj * D(D+1)/2 * 8 bytes must stay below 2 GiB per save slot; shard the ensemble");
-    HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-    if (c->jit && c->jit->rows16 && P.N < filter_rows_max_n()) {  // small ensemble: 16 lanes per trajectory, as for the compiled-in fields
-      note_kernel(P.everystep ? "odef_jit_rows_fixed_every" : "odef_jit_rows_fixed_final");
-      rc = jit_launch(P.everystep ? c->jit->rows_fixed_every : c->jit->rows_fixed_final, rows_grid(P.N), 1, &P, c->stream, 256);
-    } else if (c->jit) {
-      note_kernel(P.everystep ? "odef_jit_fixed_every" : "odef_jit_fixed_final");
-      rc = jit_launch(P.everystep ? c->jit->fixed_every : c->jit->fixed_final, (unsigned)((P.N + 63) / 64), 1, &P, c->stream);
-    } else
-      rc = launch_filter(c->cfg.rhs_id, c->q, c->cfg.alg == ODEF_EK1, 0, P, c->stream);
+    return fail(c, "odef_solve_fixed: n_traj * D(D+1)/2 * 8 bytes must stay below 2 GiB per save slot; shard the ensemble");
   }
+  HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
+  const int rc = c->field->filter(c->q, c->cfg.alg == ODEF_EK1, P, c->stream, 0, have ? c->d_stage : nullptr, have, &c->stage_filter_recs);
   if (rc) return fail(c, "odef_solve_fixed: no kernel for rhs %d order %d", c->cfg.rhs_id, c->q);
   std::snprintf(c->kname[0], sizeof c->kname[0], "%s", last_kernel());
   return finish_filter(c, 1);
@@ -664,17 +643,7 @@ int odef_solve_adaptive(odef_ctx* c, double t1, double abstol, double reltol, do
   }
   HIPCHK(c, hipMemsetAsync(c->f[ODEF_F_T].ptr, 0, c->f[ODEF_F_T].valid, c->stream));
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  int rc;
-  if (c->jit && c->jit->rows16 && P.N < filter_rows_max_n()) {
-    note_kernel("odef_jit_rows_adaptive");
-    rc = jit_launch(c->jit->rows_adaptive, rows_grid(P.N), 1, &P, c->stream, 256);
-  } else if (c->jit) {
-    note_kernel("odef_jit_adaptive");
-    rc = jit_launch(c->jit->adaptive, (unsigned)((P.N + 63) / 64), 1, &P, c->stream);
-  } else {
-    rc = c->team_path ? c->team->filter(c->q, c->cfg.alg == ODEF_EK1, P, c->stream, 1, nullptr, 0, &c->stage_filter_recs)
-                      : launch_filter(c->cfg.rhs_id, c->q, c->cfg.alg == ODEF_EK1, 1, P, c->stream);
-  }
+  const int rc = c->field->filter(c->q, c->cfg.alg == ODEF_EK1, P, c->stream, 1, nullptr, 0, &c->stage_filter_recs);
   if (rc) return fail(c, "odef_solve_adaptive: no kernel for rhs %d order %d", c->cfg.rhs_id, c->q);
   std::snprintf(c->kname[0], sizeof c->kname[0], "%s", last_kernel());
   return finish_filter(c, 1);
@@ -708,45 +677,28 @@ int odef_smooth(odef_ctx* c) {
     HIPCHK(c, hipMemsetAsync(S.smean, 0, c->f[ODEF_F_SMOOTH_MEAN].valid, c->stream));
     HIPCHK(c, hipMemsetAsync(S.scov, 0, c->f[ODEF_F_SMOOTH_COV_TRIL].valid, c->stream));
   }
-  if (c->team_path && ensure_ws(c, (size_t)c->cfg.n_traj * c->team->smooth_ws(c->q))) return -1;
+  if (c->field->smooth_ws && ensure_ws(c, (size_t)c->cfg.n_traj * c->field->smooth_ws(c->q))) return -1;
   HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
-  int rc;
-  if (c->jit)
-    if (c->jit->rows16 && S.N < smooth_rows_max_n()) {  // small ensemble: the DPP row-team smoother
-      note_kernel(S.adaptive ? "odef_jit_bcast_adapt" : "odef_jit_bcast_fixed");
-      rc = jit_launch(S.adaptive ? c->jit->bcast_adapt : c->jit->bcast_fixed, rows_grid(S.N), 1, &S, c->stream, 256);
-    } else if (c->jit->posterior) {
-      note_kernel(S.adaptive ? "odef_jit_smooth_adapt" : "odef_jit_smooth_fixed");
-      rc = jit_launch(S.adaptive ? c->jit->smooth_adapt : c->jit->smooth_fixed, (unsigned)((S.N + 63) / 64), 1, &S, c->stream);
-    } else if (c->jit->smooth_rows) {
-      const long tpb = 64 / c->jit->rows_team;
-      note_kernel("odef_jit_smooth_rows");
-      rc = jit_launch(c->jit->smooth_rows, (unsigned)((S.N + tpb - 1) / tpb), 1, &S, c->stream);
-    } else
-      rc = -3;
-  else if (c->team_path) {
-    rc = -4;
-    {  // the covariance records go through the trajectory-major stage, in blocks (record_stage.h)
-      long n_rec = S.n_save;
-      if (S.adaptive) {  // save slots in use: the largest record count of the ensemble
-        std::vector<int> ns((size_t)S.N);
-        HIPCHK(c, hipMemcpyAsync(ns.data(), S.nsaved, ns.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        n_rec = 1;
-        for (int v : ns) n_rec = v > n_rec ? v : n_rec;
-        if (n_rec > S.n_save) n_rec = S.n_save;
-      }
-      const size_t tri = (size_t)c->D * (c->D + 1) / 2;
-      const size_t per_rec = (size_t)S.N * ((tri + 15) / 16 * 16);
-      // the filter's records may still be in the stage (fixed grid, every step saved, all of them fit): record r at r * per_rec
-      const bool resident = !S.adaptive && n_rec >= 3 && c->stage_filter_recs == n_rec && c->stage_cap >= (size_t)n_rec * per_rec;
-      const size_t have = n_rec < 3 ? 0 : resident ? (size_t)(n_rec - 1) * per_rec : ensure_stage(c, n_rec - 1, per_rec);
-      if (have) rc = c->team->smooth_staged(c->q, S, n_rec, c->d_ws, c->d_stage, have, c->stream, resident ? n_rec : 0);
-      c->stage_filter_recs = 0;  // (smoothed records now, or another block layout)
+  int rc = -4;
+  if (c->field->smooth_staged) {  // the covariance records go through the trajectory-major stage, in blocks (record_stage.h)
+    long n_rec = S.n_save;
+    if (S.adaptive) {  // save slots in use: the largest record count of the ensemble
+      std::vector<int> ns((size_t)S.N);
+      HIPCHK(c, hipMemcpyAsync(ns.data(), S.nsaved, ns.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      n_rec = 1;
+      for (int v : ns) n_rec = v > n_rec ? v : n_rec;
+      if (n_rec > S.n_save) n_rec = S.n_save;
     }
-    if (rc == -4) rc = c->team->smooth(c->q, S, c->d_ws, c->stream);
-  } else
-    rc = launch_smooth(c->d, c->q, S, c->stream);
+    const size_t tri = (size_t)c->D * (c->D + 1) / 2;
+    const size_t per_rec = (size_t)S.N * ((tri + 15) / 16 * 16);
+    // the filter's records may still be in the stage (fixed grid, every step saved, all of them fit): record r at r * per_rec
+    const bool resident = !S.adaptive && n_rec >= 3 && c->stage_filter_recs == n_rec && c->stage_cap >= (size_t)n_rec * per_rec;
+    const size_t have = n_rec < 3 ? 0 : resident ? (size_t)(n_rec - 1) * per_rec : ensure_stage(c, n_rec - 1, per_rec);
+    if (have) rc = c->field->smooth_staged(c->q, S, n_rec, c->d_ws, c->d_stage, have, c->stream, resident ? n_rec : 0);
+    c->stage_filter_recs = 0;  // (smoothed records now, or another block layout)
+  }
+  if (rc == -4) rc = c->field->smooth(c->q, S, c->d_ws, c->stream);
   if (rc) return fail(c, "odef_smooth: no kernel for d %d order %d", c->d, c->q);
   std::snprintf(c->kname[1], sizeof c->kname[1], "%s", last_kernel());
   HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
@@ -763,7 +715,7 @@ int odef_dense_output(odef_ctx* c, const double* tq, int64_t n_q, int smoothed) 
   if (c->cfg.save_mode != ODEF_SAVE_EVERYSTEP) return fail(c, "odef_dense_output: needs ODEF_SAVE_EVERYSTEP");
   if (smoothed && !c->smoothed_done) return fail(c, "odef_dense_output: smoothed posterior requested but odef_smooth has not run");
   if (n_q < 1 || n_q > 65535) return fail(c, "odef_dense_output: n_q must be in 1..65535");
-  if (!c->team_path && c->D > 32) return fail(c, "odef_dense_output: built for state dimension <= 32 and for the workgroup-per-trajectory path (got %d)", c->D);
+  if (!team_path(c) && c->D > 32) return fail(c, "odef_dense_output: built for state dimension <= 32 and for the workgroup-per-trajectory path (got %d)", c->D);
   if (set_device(c)) return -1;
   if (c->tq_cap < (size_t)n_q) {
     if (c->d_tq) HIPCHK(c, hipFree(c->d_tq));
@@ -796,14 +748,36 @@ int odef_dense_output(odef_ctx* c, const double* tq, int64_t n_q, int smoothed) 
   P.n_q = (long)n_q;
   P.qmean = (double*)c->f[ODEF_F_DENSE_MEAN].ptr;
   P.qcov = (double*)c->f[ODEF_F_DENSE_COV_TRIL].ptr;
-  if (c->team_path && ensure_ws(c, (size_t)dense_d28_grid(P.N * P.n_q) * c->team->smooth_ws(c->q))) return -1;
-  const long rows_tpb = c->jit ? 64 / c->jit->rows_team : 1;
-  const int rc = c->jit ? (c->jit->posterior    ? jit_launch(c->jit->dense, (unsigned)((P.N + 63) / 64), (unsigned)P.n_q, &P, c->stream)
-                           : c->jit->dense_rows ? jit_launch(c->jit->dense_rows, (unsigned)((P.N * P.n_q + rows_tpb - 1) / rows_tpb), 1, &P, c->stream)
-                                                : -3)
-                 : c->team_path ? c->team->dense(c->q, P, c->d_ws, c->stream)
-                 : c->d == 2 ? launch_dense_d2(c->q, P, c->stream) : c->d == 3 ? launch_dense_d3(c->q, P, c->stream) : -3;
-  if (rc) return fail(c, "odef_dense_output: no kernel for d %d order %d", c->d, c->q);
+  if (c->field->smooth_ws && ensure_ws(c, (size_t)dense_d28_grid(P.N * P.n_q) * c->field->smooth_ws(c->q))) return -1;
+  if (c->field->dense(c->q, P, c->d_ws, c->stream)) return fail(c, "odef_dense_output: no kernel for d %d order %d", c->d, c->q);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+// posterior sampling (odef_sample: over the save slots; odef_dense_sample: over the filter posterior at the query times)
+static SampleParams sample_params(const odef_ctx* c, long n_rec, int mean_field, int cov_field, int64_t n_samples, uint64_t seed, double noise_scale) {
+  SampleParams S;
+  std::memset(&S, 0, sizeof S);
+  S.pc = c->pc;
+  S.N = c->cfg.n_traj;
+  S.n_save = n_rec;
+  S.adaptive = c->adaptive;
+  S.tsave = (const double*)c->f[ODEF_F_T].ptr;
+  S.nsaved = (const int*)c->f[ODEF_F_NSAVED].ptr;
+  S.mean = (const double*)c->f[mean_field].ptr;
+  S.cov = (const double*)c->f[cov_field].ptr;
+  S.diff = (const double*)c->f[ODEF_F_DIFFUSION].ptr;
+  S.n_samples = (long)n_samples;
+  S.seed = (unsigned long long)seed;
+  S.noise_scale = noise_scale;
+  S.samples = (double*)c->f[ODEF_F_SAMPLES].ptr;
+  return S;
+}
+
+static int run_sampler(odef_ctx* c, const SampleParams& S, const char* who) {
+  if (c->field->smooth_ws && ensure_ws(c, (size_t)dense_d28_grid(S.N * S.n_samples) * c->field->smooth_ws(c->q))) return -1;
+  if (c->field->sample(c->q, S, c->d_ws, c->stream)) return fail(c, "%s: no kernel for d %d order %d", who, c->d, c->q);
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -814,40 +788,16 @@ int odef_sample(odef_ctx* c, int64_t n_samples, uint64_t seed, double noise_scal
   if (!c->solved) return fail(c, "odef_sample: call odef_solve_* first");
   if (c->cfg.save_mode != ODEF_SAVE_EVERYSTEP) return fail(c, "odef_sample: needs ODEF_SAVE_EVERYSTEP (sampling not implemented for non-smoothed posteriors)");
   if (n_samples < 1 || n_samples > 65535) return fail(c, "odef_sample: n_samples must be in 1..65535");
-  if (!c->team_path && c->D > 32) return fail(c, "odef_sample: built for state dimension <= 32 and for the workgroup-per-trajectory path (got %d)", c->D);
+  if (!team_path(c) && c->D > 32) return fail(c, "odef_sample: built for state dimension <= 32 and for the workgroup-per-trajectory path (got %d)", c->D);
   if (set_device(c)) return -1;
   c->n_samples = (long)n_samples;
   if (ensure(c, ODEF_F_SAMPLES, field_count(c, ODEF_F_SAMPLES, c->n_save) * sizeof(double))) return -1;
-  SampleParams S;
-  std::memset(&S, 0, sizeof S);
-  S.pc = c->pc;
-  S.N = c->cfg.n_traj;
-  S.n_save = c->n_save;
-  S.adaptive = c->adaptive;
+  SampleParams S = sample_params(c, c->n_save, ODEF_F_MEAN, ODEF_F_COV_TRIL, n_samples, seed, noise_scale);
   S.hs = c->d_hs;
   S.ptab = c->d_ptab;
   S.tab_idx = c->d_tab_idx;
-  S.tsave = (const double*)c->f[ODEF_F_T].ptr;
-  S.nsaved = (const int*)c->f[ODEF_F_NSAVED].ptr;
-  S.mean = (const double*)c->f[ODEF_F_MEAN].ptr;
-  S.cov = (const double*)c->f[ODEF_F_COV_TRIL].ptr;
-  S.diff = (const double*)c->f[ODEF_F_DIFFUSION].ptr;
-  S.n_samples = (long)n_samples;
-  S.seed = (unsigned long long)seed;
-  S.noise_scale = noise_scale;
-  S.samples = (double*)c->f[ODEF_F_SAMPLES].ptr;
   if (c->adaptive) HIPCHK(c, hipMemsetAsync(S.samples, 0, c->f[ODEF_F_SAMPLES].valid, c->stream));  // unused slots stay defined
-  if (c->team_path && ensure_ws(c, (size_t)dense_d28_grid(S.N * S.n_samples) * c->team->smooth_ws(c->q))) return -1;
-  const long rows_tpb = c->jit ? 64 / c->jit->rows_team : 1;
-  const int rc = c->jit ? (c->jit->posterior     ? jit_launch(c->jit->sample, (unsigned)((S.N + 63) / 64), (unsigned)S.n_samples, &S, c->stream)
-                           : c->jit->sample_rows ? jit_launch(c->jit->sample_rows, (unsigned)((S.N * S.n_samples + rows_tpb - 1) / rows_tpb), 1, &S, c->stream)
-                                                 : -3)
-                 : c->team_path ? c->team->sample(c->q, S, c->d_ws, c->stream)
-                 : c->d == 2 ? launch_sample_d2(c->q, S, c->stream) : c->d == 3 ? launch_sample_d3(c->q, S, c->stream) : -3;
-  if (rc) return fail(c, "odef_sample: no kernel for d %d order %d", c->d, c->q);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return run_sampler(c, S, "odef_sample");
 }
 
 int odef_dense_sample(odef_ctx* c, const double* tq, int64_t n_q, int64_t n_samples, uint64_t seed, double noise_scale) {
@@ -858,35 +808,11 @@ int odef_dense_sample(odef_ctx* c, const double* tq, int64_t n_q, int64_t n_samp
   if (odef_dense_output(c, tq, n_q, 0)) return -1;  // filter posterior at tq (src/solution_sampling.jl:66)
   c->n_samples = (long)n_samples;
   if (ensure(c, ODEF_F_SAMPLES, field_count(c, ODEF_F_SAMPLES, (long)n_q) * sizeof(double))) return -1;
-  SampleParams S;
-  std::memset(&S, 0, sizeof S);
-  S.pc = c->pc;
-  S.N = c->cfg.n_traj;
-  S.n_save = (long)n_q;
-  S.adaptive = c->adaptive;
-  S.tsave = (const double*)c->f[ODEF_F_T].ptr;
-  S.nsaved = (const int*)c->f[ODEF_F_NSAVED].ptr;
-  S.mean = (const double*)c->f[ODEF_F_DENSE_MEAN].ptr;
-  S.cov = (const double*)c->f[ODEF_F_DENSE_COV_TRIL].ptr;
-  S.diff = (const double*)c->f[ODEF_F_DIFFUSION].ptr;
+  SampleParams S = sample_params(c, (long)n_q, ODEF_F_DENSE_MEAN, ODEF_F_DENSE_COV_TRIL, n_samples, seed, noise_scale);
   S.tq = c->d_tq;
   S.rec_t = c->d_tgrid;
   S.n_rec = c->n_save;
-  S.n_samples = (long)n_samples;
-  S.seed = (unsigned long long)seed;
-  S.noise_scale = noise_scale;
-  S.samples = (double*)c->f[ODEF_F_SAMPLES].ptr;
-  if (c->team_path && ensure_ws(c, (size_t)dense_d28_grid(S.N * S.n_samples) * c->team->smooth_ws(c->q))) return -1;
-  const long rows_tpb = c->jit ? 64 / c->jit->rows_team : 1;
-  const int rc = c->jit ? (c->jit->posterior     ? jit_launch(c->jit->sample, (unsigned)((S.N + 63) / 64), (unsigned)S.n_samples, &S, c->stream)
-                           : c->jit->sample_rows ? jit_launch(c->jit->sample_rows, (unsigned)((S.N * S.n_samples + rows_tpb - 1) / rows_tpb), 1, &S, c->stream)
-                                                 : -3)
-                 : c->team_path ? c->team->sample(c->q, S, c->d_ws, c->stream)
-                 : c->d == 2 ? launch_sample_d2(c->q, S, c->stream) : c->d == 3 ? launch_sample_d3(c->q, S, c->stream) : -3;
-  if (rc) return fail(c, "odef_dense_sample: no kernel for d %d order %d", c->d, c->q);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return 0;
+  return run_sampler(c, S, "odef_dense_sample");
 }
 
 int64_t odef_n_save(const odef_ctx* c) { return c ? c->n_save : -1; }
@@ -1318,22 +1244,16 @@ void note_kernel(const char* fmt, ...) {
 }
 const char* last_kernel() { return g_last_kernel; }
 
-int launch_filter(int rhs, int q, int ek1, int adaptive, const FilterParams& P, hipStream_t s) {
-  switch (rhs) {
-    case ODEF_RHS_FHN: return launch_filter_fhn(q, ek1, adaptive, P, s);
-    case ODEF_RHS_LORENZ63: return launch_filter_lorenz63(q, ek1, adaptive, P, s);
-    case ODEF_RHS_LOTKA_VOLTERRA: return launch_filter_lotka_volterra(q, ek1, adaptive, P, s);
-    case ODEF_RHS_VANDERPOL: return launch_filter_vanderpol(q, ek1, adaptive, P, s);
-    case ODEF_RHS_LINEAR: return launch_filter_linear(q, ek1, adaptive, P, s);
-    default: return -2;
+const FieldLaunch* field_launch(int rhs_id) {
+  switch (rhs_id) {
+    case ODEF_RHS_FHN: return field_fhn();
+    case ODEF_RHS_LORENZ63: return field_lorenz63();
+    case ODEF_RHS_LOTKA_VOLTERRA: return field_lotka_volterra();
+    case ODEF_RHS_VANDERPOL: return field_vanderpol();
+    case ODEF_RHS_LINEAR: return field_linear();
+    case ODEF_RHS_PLEIADES: return field_pleiades();
+    case ODEF_RHS_LORENZ96: return field_lorenz96();
+    default: return nullptr;
   }
-}
-const TeamLaunch* team_launch(int rhs_id) {
-  return rhs_id == ODEF_RHS_PLEIADES ? team_pleiades() : rhs_id == ODEF_RHS_LORENZ96 ? team_lorenz96() : nullptr;
-}
-int launch_smooth(int d, int q, const SmoothParams& P, hipStream_t s) {
-  if (d == 2) return launch_smooth_d2(q, P, s);
-  if (d == 3) return launch_smooth_d3(q, P, s);
-  return -2;
 }
 }  // namespace odef

@@ -10,8 +10,15 @@ inline int dispatch_alg(int ek1, F&& f) {
   else f.template operator()<RHS, q, false>();
   return 0;
 }
-template <class RHS, class F>
+// ONLYQ != 0: a translation unit built for one order and algorithm (run-time compiled fields, jit.hip) instantiates
+// (ONLYQ, ONLYEK1) alone
+template <class RHS, int ONLYQ = 0, bool ONLYEK1 = false, class F>
 inline int dispatch_order(int q, int ek1, F&& f) {
+  if constexpr (ONLYQ != 0) {
+    if (q != ONLYQ || (ek1 != 0) != ONLYEK1) return -2;
+    f.template operator()<RHS, ONLYQ, ONLYEK1>();
+    return 0;
+  } else
   switch (q) {
     case 1: return dispatch_alg<RHS, 1>(ek1, f);
     case 2: return dispatch_alg<RHS, 2>(ek1, f);
@@ -21,7 +28,7 @@ inline int dispatch_order(int q, int ek1, F&& f) {
     default: return -2;
   }
 }
-// ONLYQ != 0: a translation unit built for one order (run-time compiled fields, jit.hip) instantiates that order alone
+// ... and the same for the smoother, dense output and sampling (no algorithm: they do not evaluate the field)
 template <int d, int ONLYQ = 0, class F>
 inline int dispatch_smooth_order(int q, F&& f) {
   if constexpr (ONLYQ != 0) {

@@ -788,4 +788,36 @@ struct LaunchSmooth {
   }
 };
 
+// The launchers above with the signatures of a FieldLaunch table (launch.h); ONLYQ / ONLYEK1 as for dispatch_order
+template <class RHS, int ONLYQ = 0, bool ONLYEK1 = false>
+int lane_filter(int q, int ek1, const FilterParams& P, hipStream_t s, int adaptive, double*, size_t, long*) {
+  LaunchFilter f{P, adaptive, s};
+  return dispatch_order<RHS, ONLYQ, ONLYEK1>(q, ek1, f);
+}
+template <int d, int ONLYQ = 0>
+int lane_smooth(int q, const SmoothParams& P, double*, hipStream_t s) {
+  LaunchSmooth f{P, s};
+  return dispatch_smooth_order<d, ONLYQ>(q, f);
+}
+template <int d, int ONLYQ = 0>
+int lane_dense(int q, const DenseParams& P, double*, hipStream_t s) {
+  LaunchDense f{P, s};
+  const int rc = dispatch_smooth_order<d, ONLYQ>(q, f);
+  return rc ? rc : f.rc;
+}
+template <int d, int ONLYQ = 0>
+int lane_sample(int q, const SampleParams& P, double*, hipStream_t s) {
+  LaunchSample f{P, s};
+  const int rc = dispatch_smooth_order<d, ONLYQ>(q, f);
+  return rc ? rc : f.rc;
+}
+// the smoother, dense output and sampler of d = 2 / 3 are instantiated once, in inst_smooth_d{2,3}.hip (whose ISA listing
+// tests/test_build_hygiene.py checks); the fields' tables only point at them
+extern template int lane_smooth<2>(int, const SmoothParams&, double*, hipStream_t);
+extern template int lane_dense<2>(int, const DenseParams&, double*, hipStream_t);
+extern template int lane_sample<2>(int, const SampleParams&, double*, hipStream_t);
+extern template int lane_smooth<3>(int, const SmoothParams&, double*, hipStream_t);
+extern template int lane_dense<3>(int, const DenseParams&, double*, hipStream_t);
+extern template int lane_sample<3>(int, const SampleParams&, double*, hipStream_t);
+
 }  // namespace odef

@@ -1,7 +1,7 @@
 #include "ek_kernels.h"
 namespace odef {
-int launch_filter_lorenz63(int q, int ek1, int adaptive, const FilterParams& P, hipStream_t s) {
-  LaunchFilter f{P, adaptive, s};
-  return dispatch_order<RhsLorenz63>(q, ek1, f);
+const FieldLaunch* field_lorenz63() {
+  static const FieldLaunch t = {3, lane_filter<RhsLorenz63>, lane_smooth<3>, nullptr, lane_dense<3>, lane_sample<3>, nullptr};
+  return &t;
 }
 }  // namespace odef

@@ -1,7 +1,7 @@
 #include "ek_kernels.h"
 namespace odef {
-int launch_filter_vanderpol(int q, int ek1, int adaptive, const FilterParams& P, hipStream_t s) {
-  LaunchFilter f{P, adaptive, s};
-  return dispatch_order<RhsVanDerPol>(q, ek1, f);
+const FieldLaunch* field_vanderpol() {
+  static const FieldLaunch t = {2, lane_filter<RhsVanDerPol>, lane_smooth<2>, nullptr, lane_dense<2>, lane_sample<2>, nullptr};
+  return &t;
 }
 }  // namespace odef

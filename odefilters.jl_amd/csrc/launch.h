@@ -13,27 +13,13 @@ namespace odef {
 void note_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 const char* last_kernel();
 inline const char* tf(bool b) { return b ? "true" : "false"; }
-// returns 0, or -2 when (rhs, q) is not instantiated
-int launch_filter(int rhs, int q, int ek1, int adaptive, const FilterParams& P, hipStream_t s);
-int launch_smooth(int d, int q, const SmoothParams& P, hipStream_t s);
-// per-RHS translation units
-int launch_filter_fhn(int q, int ek1, int adaptive, const FilterParams& P, hipStream_t s);
-int launch_filter_lorenz63(int q, int ek1, int adaptive, const FilterParams& P, hipStream_t s);
-int launch_filter_lotka_volterra(int q, int ek1, int adaptive, const FilterParams& P, hipStream_t s);
-int launch_filter_vanderpol(int q, int ek1, int adaptive, const FilterParams& P, hipStream_t s);
-int launch_filter_linear(int q, int ek1, int adaptive, const FilterParams& P, hipStream_t s);
-int launch_smooth_d2(int q, const SmoothParams& P, hipStream_t s);
-int launch_smooth_d3(int q, const SmoothParams& P, hipStream_t s);
-// returns -3 when the state dimension is outside the dense-output kernel's range (D <= 12)
-int launch_dense_d2(int q, const DenseParams& P, hipStream_t s);
-int launch_dense_d3(int q, const DenseParams& P, hipStream_t s);
-int launch_sample_d2(int q, const SampleParams& P, hipStream_t s);
-int launch_sample_d3(int q, const SampleParams& P, hipStream_t s);
-// workgroup-per-trajectory path: the launch functions of one vector field (team_launch_impl.h instantiated per field) ...
-struct TeamLaunch {
+// The launch functions of one vector field, one table per field: the compiled-in ones in their inst_*.hip, a run-time
+// compiled one in the shared object jit.hip builds around it.  The launch functions return 0 on success, -2 when the order
+// (or algorithm) is not instantiated, -3 when the state dimension is outside the kernels' range.
+struct FieldLaunch {
   int d;
-  // fixed grid (adaptive = 0; every-step records through `stage` when all of them fit) or adaptive solve on the matrix-core filter
-  // `staged_recs` (may be null): set to the number of records the kernel left in `stage` (trajectory-major, record r at r N ld), 0 if none
+  // fixed grid or adaptive; workgroup-per-trajectory fields: every-step records through `stage` when all of them fit, and
+  // `staged_recs` (may be null) set to the number of records the kernel left there (trajectory-major, record r at r N ld), 0 if none
   int (*filter)(int q, int ek1, const FilterParams& P, hipStream_t s, int adaptive, double* stage, size_t stage_doubles, long* staged_recs);
   int (*smooth)(int q, const SmoothParams& P, double* ws, hipStream_t s);  // records in place
   // `filter_recs_in_stage` == n_rec: the filter's records 0 .. n_rec - 1 are still in `stage` (nothing to copy in)
@@ -41,14 +27,21 @@ struct TeamLaunch {
   int (*dense)(int q, const DenseParams& P, double* ws, hipStream_t s);    // ws: dense_d28_grid(items) x smooth_ws(q) doubles
   int (*sample)(int q, const SampleParams& P, double* ws, hipStream_t s);
   size_t (*smooth_ws)(int q);  // doubles of workspace per trajectory (smoother) / per grid slot (dense output, sampling)
+  // smooth_staged and smooth_ws are null for the lane / row-team fields (their launchers ignore `ws` and the stage): a table
+  // with them is a field on the workgroup-per-trajectory kernels
 };
-// Layout stamp of what crosses between the library and a run-time compiled module of this path (jit.hip builds one from the
-// headers it finds at run time: a tree whose headers moved on without a rebuild of the library must be refused, not launched)
+// Layout stamp of what crosses between the library and a run-time compiled module (jit.hip builds one from the headers it
+// finds at run time: a tree whose headers moved on without a rebuild of the library must be refused, not launched)
 inline unsigned long team_abi_stamp() {
-  return sizeof(FilterParams) * 1000003ul + sizeof(SmoothParams) * 10007ul + sizeof(DenseParams) * 101ul + sizeof(SampleParams) + sizeof(TeamLaunch) * 7ul;
+  return sizeof(FilterParams) * 1000003ul + sizeof(SmoothParams) * 10007ul + sizeof(DenseParams) * 101ul + sizeof(SampleParams) + sizeof(FieldLaunch) * 7ul;
 }
-const TeamLaunch* team_pleiades();  // d = 28 (BASELINE config 4)
-const TeamLaunch* team_lorenz96();  // d = 16: the same kernels on a second shape
-const TeamLaunch* team_launch(int rhs_id);  // nullptr: the field runs on the lane / row-team kernels
+const FieldLaunch* field_fhn();
+const FieldLaunch* field_lorenz63();
+const FieldLaunch* field_lotka_volterra();
+const FieldLaunch* field_vanderpol();
+const FieldLaunch* field_linear();
+const FieldLaunch* field_pleiades();  // d = 28 (BASELINE config 4)
+const FieldLaunch* field_lorenz96();  // d = 16: the same kernels on a second shape
+const FieldLaunch* field_launch(int rhs_id);  // the compiled-in fields; nullptr for any other id
 long dense_d28_grid(long items);  // grid of the dense-output / sampling kernels (workspaces of smooth_ws(q) doubles)
 }  // namespace odef

@@ -1,6 +1,6 @@
 // Host-side facts about the 16-lanes-per-trajectory kernels (rows_kernels.h): which ensemble sizes they serve and how their
-// grids are sized.  A header without dependencies: the compiled-in launchers (ek_kernels.h), the launches of run-time compiled
-// vector fields (api.hip) and the kernels' own translation units (incl. the ones jit.hip generates) all read it.
+// grids are sized.  A header without dependencies: the launchers (ek_kernels.h, for the compiled-in and the run-time compiled
+// vector fields alike) and the kernels' own translation units read it.
 #pragma once
 #include <cstdlib>
 

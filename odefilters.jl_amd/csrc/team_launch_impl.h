@@ -38,6 +38,15 @@ int team_filter_staged(int q, int ek1, const FilterParams& P, hipStream_t s, int
   if (staged_recs) *staged_recs = n_rec;  // (the stage keeps them: a smoother pass that follows need not copy them in again)
   return 0;
 }
+// ... on the matrix-core kernels alone (every field but Pleiades), as a FieldLaunch filter; ONLYQ / ONLYEK1 as for dispatch_order
+template <class RHS, int ONLYQ = 0, bool ONLYEK1 = false>
+int team_filter(int q, int ek1, const FilterParams& P, hipStream_t s, int adaptive, double* stage, size_t stage_doubles, long* staged_recs) {
+  const auto by_order = [](int q, int ek1, const FilterParams& P, hipStream_t s, int adaptive) {
+    LaunchTilesFilterT<false> f{P, s, adaptive};
+    return dispatch_order<RHS, ONLYQ, ONLYEK1>(q, ek1, f);
+  };
+  return team_filter_staged<RHS::d>(q, ek1, P, s, adaptive, stage, stage_doubles, false, by_order, staged_recs);
+}
 
 // The smoother pass with the covariance records staged trajectory-major (record_stage.h), in blocks of as many records as
 // `stage` holds, from the last record down: [records in] -> smoother launch over the block (carried state in the workspace)

@@ -1096,12 +1096,12 @@ def _l96_field():
 
 
 @pytest.mark.parametrize("kernels", ["lane", "rows"])
-def test_user_vector_field_equals_the_compiled_in_one(pkg, kernels, monkeypatch):
+def test_user_vector_field_runs_the_compiled_in_kernels(pkg, kernels, monkeypatch):
     """The same Lorenz-63 text through odef_rhs_compile (hipcc child process) and through the compiled-in registry: identical
     kernels source, so identical results -- fixed grid + smoother, adaptive, dense output, sampling.  Run-time compiled
-    fields get BOTH kernel families of the small state dimensions (round 3): one lane per trajectory, and -- below the same
-    ensemble sizes as the compiled-in fields -- 16 lanes per trajectory (rows_kernels.h); each is compared with the
-    compiled-in kernels of its own family, pinned by the launcher's environment switches."""
+    fields are launched by the launchers of the compiled-in fields (csrc/ek_kernels.h), so they pick the same kernels: one
+    lane per trajectory, or 16 lanes per trajectory (rows_kernels.h) below the same ensemble sizes; each family is pinned by
+    the launcher's environment switches and compared with the compiled-in kernels of the same names."""
     big = "1000000000"
     monkeypatch.setenv("ODEF_FILTER_ROWS_MAX_N", "0" if kernels == "lane" else big)
     monkeypatch.setenv("ODEF_SMOOTH_ROWS_MAX_N", "0" if kernels == "lane" else big)
@@ -1117,9 +1117,8 @@ def test_user_vector_field_equals_the_compiled_in_one(pkg, kernels, monkeypatch)
             sols.append(pkg.solve(ens, pkg.EK1(order=3), pkg.EnsembleHIP(), trajectories=N, **kw))
         a, b = sols
         assert b.retcode == ["Success"] * N
-        want = {("lane", False): ("odef_jit_fixed_every", "odef_jit_smooth_fixed"), ("lane", True): ("odef_jit_adaptive", "odef_jit_smooth_adapt"),
-                ("rows", False): ("odef_jit_rows_fixed_every", "odef_jit_bcast_fixed"), ("rows", True): ("odef_jit_rows_adaptive", "odef_jit_bcast_adapt")}
-        assert (b.ctx.kernel_name(0), b.ctx.kernel_name(1)) == want[kernels, adaptive]
+        want = tuple(a.ctx.kernel_name(k).replace("RhsLorenz63", "UserLorenz") for k in (0, 1))
+        assert "UserLorenz" in want[0] and (b.ctx.kernel_name(0), b.ctx.kernel_name(1)) == want
         assert ("rows" in a.ctx.kernel_name(0)) == (kernels == "rows") and ("bcast" in a.ctx.kernel_name(1)) == (kernels == "rows")
         # same source, same compiler back end; tolerances only allow for a different contraction/scheduling choice
         # (higher-derivative components amplify one ulp, tests/_parity.py)
@@ -1195,7 +1194,7 @@ def test_user_vector_field_on_the_matrix_core_kernels(pkg):
     """A user vector field ABOVE state dimension 20: Lorenz-96 with 12 variables at order 2 (D = 36; no compiled-in field has
     d = 12, and the struct has no `jac`).  odef_rhs_compile builds the workgroup-per-trajectory kernels of csrc/filter_mfma.h /
     smooth_mfma.h / dense_mfma.h around it for this one order and algorithm -- with their host-side launch code, as a shared
-    object that exports the launch table (csrc/jit.hip, team_translation_unit) -- and the context runs on it like on a
+    object that exports the launch table (csrc/jit.hip, module_source) -- and the context runs on it like on a
     compiled-in field: fixed grid filter (forward-mode Jacobian on one lane of the helper wavefront) + split-pass smoother
     against the oracle at the oracle's rounding-noise level, the adaptive filter against the oracle's controller loop, sol(t)."""
     d, q, name = 12, 2, "UserL96d12"
@@ -1288,7 +1287,7 @@ def test_matrix_core_filter_reads_no_lds_it_did_not_write(pkg, d, q, monkeypatch
     assert P.cov_err(sol.x_smooth_cov()[0], ref.covs(smoothed=True)) < 1e-5
 
 
-def test_user_vector_field_on_the_row_team_kernels_at_config2_size(pkg):
+def test_user_vector_field_takes_the_compiled_in_kernels_at_config2_size(pkg):
     """A user vector field with d = 5 at order 2 (D = 15: no compiled-in kernel has this shape) and 4 096 trajectories -- the
     ensemble size of BASELINE config 2, where the lane kernels would occupy 64 of the chip's 1 024 SIMDs: the library must
     pick the run-time compiled 16-lanes-per-trajectory filter and smoother (asked through odef_kernel_name, not assumed), and
@@ -1315,7 +1314,8 @@ def test_user_vector_field_on_the_row_team_kernels_at_config2_size(pkg):
     ens = pkg.EnsembleProblem(pkg.ODEProblem(name, vf.u0, vf.tspan, vf.p), perturb_scale=1e-2)
     sol = pkg.solve(ens, pkg.EK1(order=q), pkg.EnsembleHIP(), trajectories=N, dt=dt, adaptive=False)
     assert sol.retcode == ["Success"] * N
-    assert sol.ctx.kernel_name(0) == "odef_jit_rows_fixed_every" and sol.ctx.kernel_name(1) == "odef_jit_bcast_fixed"
+    assert sol.ctx.kernel_name(0) == f"odef::ek_filter_rows_kernel<odef::{name}, 2, true, true>"
+    assert sol.ctx.kernel_name(1) == "odef::rts_smooth_bcast_kernel<5, 2, false>"
     u0s = orc.ensemble_u0(vf.u0, N, 1e-2)
     mf, ms, cs = sol.x_filt_mean(), sol.x_smooth_mean(), sol.x_smooth_cov()
     for i in (0, 17, 4095):
@@ -1330,7 +1330,9 @@ def test_user_vector_field_on_the_row_team_kernels_at_config2_size(pkg):
         _os.environ["ODEF_FILTER_ROWS_MAX_N"] = "0"
         _os.environ["ODEF_SMOOTH_ROWS_MAX_N"] = "0"
         lane = pkg.solve(ens, pkg.EK1(order=q), pkg.EnsembleHIP(), trajectories=N, dt=dt, adaptive=False)
-        assert lane.ctx.kernel_name(0) == "odef_jit_fixed_every" and lane.ctx.kernel_name(1) == "odef_jit_smooth_rows"
+        # (the every-step lane filter of an ensemble below ODEF_FILTER_LAG_MAX_N stores its records one step late)
+        assert lane.ctx.kernel_name(0) == f"odef::ek_filter_fixed_kernel<odef::{name}, 2, true, true, true>"
+        assert lane.ctx.kernel_name(1) == "odef::rts_smooth_kernel<5, 2>"
         np.testing.assert_allclose(ms[..., :d], lane.x_smooth_mean()[..., :d], rtol=1e-9, atol=1e-12)
     finally:
         for k, v in old.items():
