@@ -48,6 +48,7 @@
  *   COV_TRIL    [n_save][TRI][N]   packed lower triangle, element (i,j), i>=j at i(i+1)/2+j, of
  *                                  Sigma = L L'  (`SquarerootMatrix.mat`, src/squarerootmatrix.jl:16)
  *   DIFFUSION   [n_save][N]        entry s = global diffusion of the step that produced save s (s>=1); [0]=0
+ *               [n_save][d][N]     MV models (:dynamicMV / :fixedMV): the diagonal of that global diffusion; [0][.]=0
  *   T           [n_save] (fixed)   or [n_save][N] (adaptive)
  *   LOGLIK      [N]                sum of per-accepted-step log-likelihoods (src/perform_step.jl:66,91)
  *   NACCEPT, NREJECT, NF, NJAC     int32 [N]   (destats)
@@ -71,8 +72,17 @@ extern "C" {
 typedef struct odef_ctx odef_ctx;
 
 typedef enum { ODEF_EK0 = 0, ODEF_EK1 = 1 } odef_alg;
-/* diffusionmodel = :dynamic / :fixed / :fixedMAP (src/caches.jl:89-96, src/diffusions.jl:11-36, 46-68, 71-80) */
-typedef enum { ODEF_DIFFUSION_DYNAMIC = 0, ODEF_DIFFUSION_FIXED = 1, ODEF_DIFFUSION_FIXED_MAP = 2 } odef_diffusion;
+/* diffusionmodel = :dynamic / :fixed / :fixedMAP / :dynamicMV / :fixedMV (src/caches.jl:89-96, src/diffusions.jl:11-36, 46-68,
+ * 71-80, 83-153).  The MV ("multivariate") models calibrate one diffusion per state component, Sigma = diag(sigma_1..sigma_d);
+ * they require EK0 and run on the lane kernels only (state dimension d(q+1) <= 20 and d <= 10: not Pleiades, not Lorenz-96),
+ * odef_create refuses anything else.  Their ODEF_F_DIFFUSION field is [n_save][d][N]. */
+typedef enum {
+  ODEF_DIFFUSION_DYNAMIC = 0,
+  ODEF_DIFFUSION_FIXED = 1,
+  ODEF_DIFFUSION_FIXED_MAP = 2,
+  ODEF_DIFFUSION_DYNAMIC_MV = 3,
+  ODEF_DIFFUSION_FIXED_MV = 4
+} odef_diffusion;
 typedef enum {
   ODEF_RHS_FHN = 0,            /* u' = (c(u1 - u1^3/3 + u2), -(u1 - a - b u2)/c), p = (a,b,c) */
   ODEF_RHS_LORENZ63 = 1,       /* p = (sigma, rho, beta) */

@@ -9,6 +9,7 @@ module ODEFilterHIP
 
 using ProbNumDiffEq            # EK0, EK1 (src/algorithms.jl:23-51)
 import DiffEqBase
+using LinearAlgebra: Diagonal  # sol.diffusions of the MV models
 
 const LIB = get(ENV, "ODEFILTER_HIP_LIB", "libodefilter_hip.so")
 
@@ -20,7 +21,9 @@ struct OdefConfig                      # odef_config, 56 bytes
 end
 
 const RHS_IDS = Dict(:fhn => 0, :lorenz63 => 1, :lotka_volterra => 2, :vanderpol => 3, :linear => 4, :pleiades => 5, :lorenz96 => 6)
-const DIFFUSIONS = Dict(:dynamic => 0, :fixed => 1, :fixedMAP => 2)   # src/caches.jl:89-96 (the MV models are not on the device)
+# src/caches.jl:89-96; the MV models (diagonal diffusion, EK0 only, the lane kernels: d(q+1) <= 20) keep d diffusions per save
+const DIFFUSIONS = Dict(:dynamic => 0, :fixed => 1, :fixedMAP => 2, :dynamicMV => 3, :fixedMV => 4)
+const MV_DIFFUSIONS = (:dynamicMV, :fixedMV)
 const F_MEAN, F_COV_TRIL, F_DIFFUSION, F_T, F_LOGLIK, F_NACCEPT, F_NREJECT, F_NF, F_NJAC, F_NSAVED,
       F_RETCODE, F_SMOOTH_MEAN, F_SMOOTH_COV_TRIL = 0:12
 const F_SAMPLES = 16
@@ -93,6 +96,8 @@ function DiffEqBase.__solve(eprob::DiffEqBase.EnsembleProblem, alg::Union{EK0,EK
     q = alg.order; D = d * (q + 1); TRI = D * (D + 1) ÷ 2
     p = collect(Float64, prob.p)
     !adaptive && dt === nothing && error("Fixed timestep methods require a choice of dt or choosing the tstops")
+    mv = alg.diffusionmodel in MV_DIFFUSIONS
+    mv && alg isa EK1 && error("MV diffusion models require EK0")   # src/diffusions.jl:96, :125
     cfg = Ref(OdefConfig(sizeof(OdefConfig), alg isa EK1 ? 1 : 0, q, DIFFUSIONS[alg.diffusionmodel],
                          alg.smooth ? 1 : 0, RHS_IDS[ealg.rhs], d, length(p), 1, 1, ealg.device, 1, N))
     h = Ref{Ptr{Cvoid}}(C_NULL)
@@ -140,7 +145,9 @@ function DiffEqBase.__solve(eprob::DiffEqBase.EnsembleProblem, alg::Union{EK0,EK
         return (t = tsave, keep = keep, samples = samples, dense_samples = dense_samples,
                 u = view(mean, :, 1:d, :), x_mean = mean, x_cov_tril = cov,
                 x_filt_mean = fetch(ctx, F_MEAN, Float64, N, D, ns),
-                diffusions = fetch(ctx, F_DIFFUSION, Float64, N, ns)[:, 2:end],
+                # MV models: [n_save][d][N] on the device, one Diagonal(sigma_1..sigma_d) per trajectory and step
+                diffusions = mv ? (dv = fetch(ctx, F_DIFFUSION, Float64, N, d, ns); [Diagonal(dv[i, :, s]) for i in 1:N, s in 2:ns])
+                                : fetch(ctx, F_DIFFUSION, Float64, N, ns)[:, 2:end],
                 log_likelihood = fetch(ctx, F_LOGLIK, Float64, N),
                 destats = (nf = fetch(ctx, F_NF, Int32, N), njacs = fetch(ctx, F_NJAC, Int32, N),
                            naccept = fetch(ctx, F_NACCEPT, Int32, N), nreject = fetch(ctx, F_NREJECT, Int32, N)),

@@ -86,6 +86,8 @@ namespace {
 
 // the field runs on the workgroup-per-trajectory kernels (large state dimension)
 bool team_path(const odef_ctx* c) { return c->field->smooth_staged != nullptr; }
+// the MV diffusion models :dynamicMV / :fixedMV: d diffusions per record
+bool is_mv(int diffusion) { return diffusion == ODEF_DIFFUSION_DYNAMIC_MV || diffusion == ODEF_DIFFUSION_FIXED_MV; }
 
 int fail(odef_ctx* c, const char* fmt, ...) {
   char buf[512];
@@ -153,7 +155,7 @@ size_t field_count(const odef_ctx* c, int field, long n_save) {
   switch (field) {
     case ODEF_F_MEAN: case ODEF_F_SMOOTH_MEAN: return (size_t)n_save * c->D * N;
     case ODEF_F_COV_TRIL: case ODEF_F_SMOOTH_COV_TRIL: return (size_t)n_save * c->TRI * N;
-    case ODEF_F_DIFFUSION: return (size_t)n_save * N;
+    case ODEF_F_DIFFUSION: return (size_t)n_save * (is_mv(c->cfg.diffusion) ? (size_t)c->d : 1) * N;
     case ODEF_F_T: return c->adaptive ? (size_t)n_save * N : (size_t)n_save;
     case ODEF_F_U0: return (size_t)c->d * N;
     case ODEF_F_DENSE_MEAN: return (size_t)c->n_q * c->D * N;
@@ -282,6 +284,36 @@ __global__ void scale_cov_kernel(double* __restrict__ cov, double* __restrict__ 
   loglik[i] = __builtin_nan("");
 }
 
+// postamble! of :fixedMV (src/integrator_utils.jl:4-18): with the final global diffusion diag(s_1 .. s_d) of the trajectory,
+// every filter covariance becomes sqrt(D) Sigma sqrt(D), D = kron(I, diag(s)) -- entry ((J, a), (K, b)) times sqrt(s_a s_b) --,
+// every diffusion record becomes the final one, sol.log_likelihood = NaN.  diff: [n_save][d][N].
+__global__ void scale_cov_mv_kernel(double* __restrict__ cov, double* __restrict__ diff, double* __restrict__ loglik,
+                                    const int* __restrict__ nsaved, long N, long n_save_fixed, int d, int D) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const long n_save = nsaved ? (long)nsaved[i] : n_save_fixed;
+  const bool final_only = !nsaved && n_save_fixed == 1;
+  if (!final_only && n_save < 2) {
+    loglik[i] = __builtin_nan("");
+    return;
+  }
+  double fin[10], rs[10];  // s_a and sqrt(s_a); odef_create admits the MV models for d <= 10 only
+  for (int a = 0; a < d; ++a) {
+    fin[a] = diff[((size_t)(n_save - 1) * d + a) * N + i];
+    rs[a] = sqrt(fin[a]);
+  }
+  for (long n = 0; n < n_save; ++n) {
+    for (int r = 0; r < D; ++r)
+      for (int c = 0; c <= r; ++c) {
+        const size_t k = (size_t)r * (r + 1) / 2 + c;
+        cov[((size_t)n * D * (D + 1) / 2 + k) * N + i] *= rs[r % d] * rs[c % d];
+      }
+    if (n >= 1)
+      for (int a = 0; a < d; ++a) diff[((size_t)n * d + a) * N + i] = fin[a];
+  }
+  loglik[i] = __builtin_nan("");
+}
+
 }  // namespace
 
 extern "C" {
@@ -318,8 +350,20 @@ int odef_create(odef_ctx** out, const odef_config* cfg) {
   if (cfg->n_params != ri.np) return fail(nullptr, "odef_create: rhs %d has %d parameters, got %d", cfg->rhs_id, ri.np, cfg->n_params);
   if (cfg->order < 1 || cfg->order > ODEF_MAX_ORDER) return fail(nullptr, "odef_create: order %d outside 1..%d", cfg->order, ODEF_MAX_ORDER);
   if (cfg->alg != ODEF_EK0 && cfg->alg != ODEF_EK1) return fail(nullptr, "odef_create: unknown alg %d", cfg->alg);
-  if (cfg->diffusion != ODEF_DIFFUSION_DYNAMIC && cfg->diffusion != ODEF_DIFFUSION_FIXED && cfg->diffusion != ODEF_DIFFUSION_FIXED_MAP)
+  if (cfg->diffusion != ODEF_DIFFUSION_DYNAMIC && cfg->diffusion != ODEF_DIFFUSION_FIXED && cfg->diffusion != ODEF_DIFFUSION_FIXED_MAP &&
+      !is_mv(cfg->diffusion))
     return fail(nullptr, "odef_create: unknown diffusion model %d", cfg->diffusion);
+  if (is_mv(cfg->diffusion)) {
+    // the reference asserts H == E1 * PI (src/diffusions.jl:96, :125)
+    if (cfg->alg != ODEF_EK0) return fail(nullptr, "odef_create: MV diffusion models require EK0");
+    // the MV models are built on the lane / row-team kernels only
+    const bool team = cfg->rhs_id >= kJitFirstId ? jit_team_path(cfg->d, cfg->order)
+                                                 : (cfg->rhs_id == ODEF_RHS_PLEIADES || cfg->rhs_id == ODEF_RHS_LORENZ96);
+    if (team)
+      return fail(nullptr, "odef_create: MV diffusion models run on the lane kernels only (state dimension d(q+1) <= 20, d <= 10); "
+                           "rhs %d with d = %d, d(q+1) = %d runs on the workgroup-per-trajectory kernels", cfg->rhs_id, cfg->d,
+                  cfg->d * (cfg->order + 1));
+  }
   if (cfg->n_traj <= 0) return fail(nullptr, "odef_create: n_traj must be positive");
   // run-time compiled fields: lane / row-team kernels up to state dimension 20 (d <= 10), the workgroup-per-trajectory kernels above
   if (cfg->rhs_id >= kJitFirstId && jit_team_path(cfg->d, cfg->order) && (cfg->d % 2 != 0 || cfg->d > 32 || cfg->d * (cfg->order + 1) > 176))
@@ -343,7 +387,7 @@ int odef_create(odef_ctx** out, const odef_config* cfg) {
   c->field = field_launch(cfg->rhs_id);
   if (!c->field) {
     std::string jerr;
-    c->field = jit_field(cfg->rhs_id, c->q, cfg->alg == ODEF_EK1, team_abi_stamp(), jerr);
+    c->field = jit_field(cfg->rhs_id, c->q, cfg->alg == ODEF_EK1, is_mv(cfg->diffusion), team_abi_stamp(), jerr);
     if (!c->field) {
       g_create_error = "odef_create: " + jerr;  // the whole compiler log
       delete c;
@@ -474,7 +518,7 @@ static void fill_params(odef_ctx* c, FilterParams& P) {
   P.p_shared = c->cfg.params_shared;
   P.N = c->cfg.n_traj;
   P.everystep = c->cfg.save_mode == ODEF_SAVE_EVERYSTEP;
-  P.fixed_diffusion = (int)c->cfg.diffusion;  // 0 dynamic, 1 fixed, 2 fixedMAP (static_diffusion_update, ek_math.h)
+  P.fixed_diffusion = (int)c->cfg.diffusion;  // 0 dynamic, 1 fixed, 2 fixedMAP (static_diffusion_update, ek_math.h), 3 / 4 dynamicMV / fixedMV
   P.want_loglik = c->cfg.want_loglik;
   {
     const char* e = getenv("ODEF_STAGGER");
@@ -507,7 +551,15 @@ static int complete_pending(odef_ctx* c) {
 
 static int finish_filter(odef_ctx* c, int nlaunch) {
   // static diffusion: rescale all covariances by the final global diffusion (src/integrator_utils.jl:4-18)
-  if (c->cfg.diffusion != ODEF_DIFFUSION_DYNAMIC) {
+  if (c->cfg.diffusion == ODEF_DIFFUSION_FIXED_MV) {
+    const long N = c->cfg.n_traj;
+    hipLaunchKernelGGL(scale_cov_mv_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, c->stream,
+                       (double*)c->f[ODEF_F_COV_TRIL].ptr, (double*)c->f[ODEF_F_DIFFUSION].ptr,
+                       (double*)c->f[ODEF_F_LOGLIK].ptr, c->adaptive ? (const int*)c->f[ODEF_F_NSAVED].ptr : (const int*)nullptr,
+                       N, c->n_save, c->d, c->D);
+    ++nlaunch;
+    c->stage_filter_recs = 0;
+  } else if (c->cfg.diffusion != ODEF_DIFFUSION_DYNAMIC && c->cfg.diffusion != ODEF_DIFFUSION_DYNAMIC_MV) {
     const long N = c->cfg.n_traj;
     hipLaunchKernelGGL(scale_cov_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, c->stream,
                        (double*)c->f[ODEF_F_COV_TRIL].ptr, (double*)c->f[ODEF_F_DIFFUSION].ptr,
@@ -673,6 +725,7 @@ int odef_smooth(odef_ctx* c) {
   S.smean = (double*)c->f[ODEF_F_SMOOTH_MEAN].ptr;
   S.scov = (double*)c->f[ODEF_F_SMOOTH_COV_TRIL].ptr;
   S.retcode = (int*)c->f[ODEF_F_RETCODE].ptr;
+  S.mv = is_mv(c->cfg.diffusion);
   if (c->adaptive) {  // unused save slots stay defined
     HIPCHK(c, hipMemsetAsync(S.smean, 0, c->f[ODEF_F_SMOOTH_MEAN].valid, c->stream));
     HIPCHK(c, hipMemsetAsync(S.scov, 0, c->f[ODEF_F_SMOOTH_COV_TRIL].valid, c->stream));
@@ -748,6 +801,7 @@ int odef_dense_output(odef_ctx* c, const double* tq, int64_t n_q, int smoothed) 
   P.n_q = (long)n_q;
   P.qmean = (double*)c->f[ODEF_F_DENSE_MEAN].ptr;
   P.qcov = (double*)c->f[ODEF_F_DENSE_COV_TRIL].ptr;
+  P.mv = is_mv(c->cfg.diffusion);
   if (c->field->smooth_ws && ensure_ws(c, (size_t)dense_d28_grid(P.N * P.n_q) * c->field->smooth_ws(c->q))) return -1;
   if (c->field->dense(c->q, P, c->d_ws, c->stream)) return fail(c, "odef_dense_output: no kernel for d %d order %d", c->d, c->q);
   HIPCHK(c, hipGetLastError());
@@ -772,6 +826,7 @@ static SampleParams sample_params(const odef_ctx* c, long n_rec, int mean_field,
   S.seed = (unsigned long long)seed;
   S.noise_scale = noise_scale;
   S.samples = (double*)c->f[ODEF_F_SAMPLES].ptr;
+  S.mv = is_mv(c->cfg.diffusion);
   return S;
 }
 

@@ -24,6 +24,7 @@ struct DenseParams {
   long n_q;
   double* qmean;         // [n_q][D][N]
   double* qcov;          // [n_q][TRI][N]
+  int mv;                // diff holds d diffusions per record (the MV diffusion models)
 };
 
 template <int q>
@@ -37,7 +38,7 @@ __device__ inline void precond_from_h(double h, double (&pj)[q + 1], double (&pi
   }
 }
 
-template <int d, int q>
+template <int d, int q, bool MV = false>
 __device__ inline void dense_lane(const DenseParams& P, long i, long jq, const LaneMem& xl) {
   constexpr int NB = q + 1, D = d * NB, TRI = D * (D + 1) / 2;
   const size_t N = (size_t)P.N;
@@ -70,7 +71,7 @@ __device__ inline void dense_lane(const DenseParams& P, long i, long jq, const L
   }
   // diffusions[min(idx, end)] (src/solution.jl:181): slot s holds the diffusion of step s-1 -> s
   const long sd = (idx < n - 1) ? idx : n - 1;
-  const double sigma2 = P.diff[(size_t)sd * N + i];
+  const auto sigma2 = load_sig<d, MV>(P.diff, (size_t)sd, N, (size_t)i);
   // extrapolate: goal_pred = P1^-1 predict(P1 prev, A, Qh)  (src/solution.jl:184-189)
   const double h1 = tval - tat(il);
   double pj1[NB], pij1[NB];

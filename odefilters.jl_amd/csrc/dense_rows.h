@@ -8,7 +8,7 @@
 
 namespace odef {
 
-template <int d, int q, int TEAM>
+template <int d, int q, int TEAM, bool MV = false>
 __device__ inline void dense_rows_lane(const DenseParams& P, long i, long jq, int tid, double* __restrict__ ws, RowState<d*(q + 1)>* st) {
   constexpr int NB = q + 1, D = d * NB, TRI = D * (D + 1) / 2;
   const size_t N = (size_t)P.N;
@@ -43,7 +43,7 @@ _Pragma("unroll")
     return;
   }
   const long sd = (idx < n - 1) ? idx : n - 1;  // diffusions[min(idx, end)] (src/solution.jl:181)
-  const double sigma2 = P.diff[(size_t)sd * N + i];
+  const auto sigma2 = load_sig<d, MV>(P.diff, (size_t)sd, N, (size_t)i);
   const double h1 = tval - tat(il);
   double pj1[NB], pij1[NB];
   precond_from_h<q>(h1, pj1, pij1);

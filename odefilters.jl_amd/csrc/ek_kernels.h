@@ -47,6 +47,22 @@ __global__ __launch_bounds__(kWave) void ek_filter_adaptive_kernel(const FilterP
   const long i0 = (long)blockIdx.x * kWave;
   if (i0 + threadIdx.x < P.N) filter_adaptive_lane<RHS, q, EK1>(P, i0, threadIdx.x);
 }
+// The same two kernels for the MV diffusion models :dynamicMV / :fixedMV (EK0 only; P.fixed_diffusion = 3 / 4), d diffusions per
+// record.  Kernels of their own, so that the scalar-model kernels above stay what they are.
+template <class RHS, int q, bool EVERY, bool LAG>
+__global__ __launch_bounds__(kWave) void ek_filter_fixed_mv_kernel(const FilterParams P) {
+  const long i0 = (long)blockIdx.x * kWave;
+  if (P.stagger > 0) {
+    const int n = (int)(blockIdx.x % 16u) * P.stagger;
+    for (int k = 0; k < n; ++k) __builtin_amdgcn_s_sleep(1);
+  }
+  if (i0 + threadIdx.x < P.N) filter_fixed_lane<RHS, q, false, EVERY, LAG, true>(P, i0, threadIdx.x);
+}
+template <class RHS, int q>
+__global__ __launch_bounds__(kWave) void ek_filter_adaptive_mv_kernel(const FilterParams P) {
+  const long i0 = (long)blockIdx.x * kWave;
+  if (i0 + threadIdx.x < P.N) filter_adaptive_lane<RHS, q, false, true>(P, i0, threadIdx.x);
+}
 // Smoother: row-per-lane teams (smooth_rows.h), 16 lanes per trajectory for D <= 16 (4 trajectories per
 // wavefront), 32 lanes for D <= 32; per-team matrices in LDS.
 template <int D>
@@ -60,6 +76,17 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_num_vgpr(128))) void r
   const long i = (long)blockIdx.x * TPB + team;
   RowState<D> st;
   if (i < P.N) smooth_rows_lane<d, q, TEAM>(P, i, tid, lds + team * W::size, &st);
+}
+// ... for the MV diffusion models (d diffusions per record): the one smoother of those models, at every ensemble size
+template <int d, int q>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_num_vgpr(128))) void rts_smooth_mv_kernel(const SmoothParams P) {
+  constexpr int D = d * (q + 1), TEAM = SmoothTeam<D>::lanes, TPB = kWave / TEAM;
+  using W = RowsWs<d, q + 1>;
+  __shared__ double lds[TPB * W::size];
+  const int team = threadIdx.x / TEAM, tid = threadIdx.x % TEAM;
+  const long i = (long)blockIdx.x * TPB + team;
+  RowState<D> st;
+  if (i < P.N) smooth_rows_lane<d, q, TEAM, true>(P, i, tid, lds + team * W::size, &st);
 }
 // Smoother, one lane per trajectory (D <= 12): the read-only filter covariance of the step sits in
 // lane-private LDS (78 doubles x 64 lanes = 39 KB per wave at D = 12), everything else in registers.
@@ -101,6 +128,14 @@ __global__ __launch_bounds__(kWave) void dense_output_kernel(const DenseParams P
   const LaneMem xl{lds + threadIdx.x, kWave};
   if (i < P.N) dense_lane<d, q>(P, i, (long)blockIdx.y, xl);
 }
+template <int d, int q>
+__global__ __launch_bounds__(kWave) void dense_output_mv_kernel(const DenseParams P) {
+  constexpr int D = d * (q + 1), TRI = D * (D + 1) / 2;
+  __shared__ double lds[TRI * kWave];
+  const long i = (long)blockIdx.x * kWave + threadIdx.x;
+  const LaneMem xl{lds + threadIdx.x, kWave};
+  if (i < P.N) dense_lane<d, q, true>(P, i, (long)blockIdx.y, xl);
+}
 // ... and 12 < D <= 32: one row-per-lane team per (trajectory, query time) item (dense_rows.h)
 template <int d, int q>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_num_vgpr(128))) void dense_rows_kernel(const DenseParams P) {
@@ -112,12 +147,37 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_num_vgpr(128))) void d
   RowState<D> st;
   if (it < P.N * P.n_q) dense_rows_lane<d, q, TEAM>(P, it % P.N, it / P.N, tid, lds + team * W::size, &st);
 }
-struct LaunchDense {
+template <int d, int q>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_num_vgpr(128))) void dense_rows_mv_kernel(const DenseParams P) {
+  constexpr int D = d * (q + 1), TEAM = SmoothTeam<D>::lanes, TPB = kWave / TEAM;
+  using W = RowsWs<d, q + 1>;
+  __shared__ double lds[TPB * W::size];
+  const int team = threadIdx.x / TEAM, tid = threadIdx.x % TEAM;
+  const long it = (long)blockIdx.x * TPB + team;
+  RowState<D> st;
+  if (it < P.N * P.n_q) dense_rows_lane<d, q, TEAM, true>(P, it % P.N, it / P.N, tid, lds + team * W::size, &st);
+}
+// WITH_MV: the kernels of the MV diffusion models (P.mv) are instantiated beside the scalar ones
+template <bool WITH_MV = true>
+struct LaunchDenseT {
   const DenseParams& P;
   hipStream_t s;
   int rc = 0;
   template <int d, int q>
   void operator()() {
+    if (P.mv) {
+      if constexpr (WITH_MV && d * (q + 1) <= kSmoothLaneMaxD) {
+        dim3 grid((unsigned)((P.N + kWave - 1) / kWave), (unsigned)P.n_q);
+        hipLaunchKernelGGL((dense_output_mv_kernel<d, q>), grid, dim3(kWave), 0, s, P);
+      } else if constexpr (WITH_MV && d * (q + 1) <= 32) {
+        constexpr int TPB = kWave / SmoothTeam<d*(q + 1)>::lanes;
+        const long items = P.N * P.n_q;
+        hipLaunchKernelGGL((dense_rows_mv_kernel<d, q>), dim3((unsigned)((items + TPB - 1) / TPB)), dim3(kWave), 0, s, P);
+      } else {
+        rc = -2;
+      }
+      return;
+    }
     if constexpr (d * (q + 1) <= kSmoothLaneMaxD) {
       dim3 grid((unsigned)((P.N + kWave - 1) / kWave), (unsigned)P.n_q);
       hipLaunchKernelGGL((dense_output_kernel<d, q>), grid, dim3(kWave), 0, s, P);
@@ -142,6 +202,16 @@ __global__ __launch_bounds__(kWave) void sample_kernel(const SampleParams P) {
   const long n_hi = (P.adaptive && !P.tq) ? wave_uniform_max(valid ? (long)P.nsaved[i] : 0, valid) : P.n_save;
   if (valid) sample_lane<d, q>(P, i, (long)blockIdx.y, xl, n_hi);
 }
+template <int d, int q>
+__global__ __launch_bounds__(kWave) void sample_mv_kernel(const SampleParams P) {
+  constexpr int D = d * (q + 1), TRI = D * (D + 1) / 2;
+  __shared__ double lds[TRI * kWave];
+  const long i = (long)blockIdx.x * kWave + threadIdx.x;
+  const LaneMem xl{lds + threadIdx.x, kWave};
+  const bool valid = i < P.N;
+  const long n_hi = (P.adaptive && !P.tq) ? wave_uniform_max(valid ? (long)P.nsaved[i] : 0, valid) : P.n_save;
+  if (valid) sample_lane<d, q, true>(P, i, (long)blockIdx.y, xl, n_hi);
+}
 // ... and 12 < D <= 32: one row-per-lane team per (trajectory, sample) item (sample_rows.h)
 template <int d, int q>
 __global__ __launch_bounds__(kWave) __attribute__((amdgpu_num_vgpr(128))) void sample_rows_kernel(const SampleParams P) {
@@ -153,12 +223,36 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_num_vgpr(128))) void s
   RowState<D> st;
   if (it < P.N * P.n_samples) sample_rows_lane<d, q, TEAM>(P, it % P.N, it / P.N, tid, lds + team * W::size, &st);
 }
-struct LaunchSample {
+template <int d, int q>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_num_vgpr(128))) void sample_rows_mv_kernel(const SampleParams P) {
+  constexpr int D = d * (q + 1), TEAM = SmoothTeam<D>::lanes, TPB = kWave / TEAM;
+  using W = RowsWs<d, q + 1>;
+  __shared__ double lds[TPB * W::size];
+  const int team = threadIdx.x / TEAM, tid = threadIdx.x % TEAM;
+  const long it = (long)blockIdx.x * TPB + team;
+  RowState<D> st;
+  if (it < P.N * P.n_samples) sample_rows_lane<d, q, TEAM, true>(P, it % P.N, it / P.N, tid, lds + team * W::size, &st);
+}
+template <bool WITH_MV = true>
+struct LaunchSampleT {
   const SampleParams& P;
   hipStream_t s;
   int rc = 0;
   template <int d, int q>
   void operator()() {
+    if (P.mv) {
+      if constexpr (WITH_MV && d * (q + 1) <= kSmoothLaneMaxD) {
+        const dim3 grid((unsigned)((P.N + kWave - 1) / kWave), (unsigned)P.n_samples);
+        hipLaunchKernelGGL((sample_mv_kernel<d, q>), grid, dim3(kWave), 0, s, P);
+      } else if constexpr (WITH_MV && d * (q + 1) <= 32) {
+        constexpr int TPB = kWave / SmoothTeam<d*(q + 1)>::lanes;
+        const long items = P.N * P.n_samples;
+        hipLaunchKernelGGL((sample_rows_mv_kernel<d, q>), dim3((unsigned)((items + TPB - 1) / TPB)), dim3(kWave), 0, s, P);
+      } else {
+        rc = -2;
+      }
+      return;
+    }
     if constexpr (d * (q + 1) <= kSmoothLaneMaxD) {
       const dim3 grid((unsigned)((P.N + kWave - 1) / kWave), (unsigned)P.n_samples);
       hipLaunchKernelGGL((sample_kernel<d, q>), grid, dim3(kWave), 0, s, P);
@@ -716,13 +810,34 @@ struct LaunchTeamSmooth {
   }
 };
 
-struct LaunchFilter {
+// WITH_MV: the MV-model kernels (EK0) are instantiated beside the scalar ones.  An MV context (P.fixed_diffusion 3 / 4) takes
+// the lane kernels at every ensemble size: the row-team filters (rows_filter.h) carry the scalar models only.
+template <bool WITH_MV = true>
+struct LaunchFilterT {
   const FilterParams& P;
   int adaptive;
   hipStream_t s;
+  int rc = 0;
   template <class RHS, int q, bool EK1>
   void operator()() {
     const unsigned grid = (unsigned)((P.N + kWave - 1) / kWave);
+    if (P.fixed_diffusion >= 3) {
+      if constexpr (WITH_MV && !EK1) {
+        if (adaptive) {
+          note_kernel("odef::ek_filter_adaptive_mv_kernel<odef::%s, %d>", RHS::name, q);
+          hipLaunchKernelGGL((ek_filter_adaptive_mv_kernel<RHS, q>), dim3(grid), dim3(kWave), 0, s, P);
+          return;
+        }
+        const bool lag = P.everystep && P.N < filter_lag_max_n();
+        note_kernel("odef::ek_filter_fixed_mv_kernel<odef::%s, %d, %s, %s>", RHS::name, q, tf(P.everystep), tf(lag));
+        if (lag) hipLaunchKernelGGL((ek_filter_fixed_mv_kernel<RHS, q, true, true>), dim3(grid), dim3(kWave), 0, s, P);
+        else if (P.everystep) hipLaunchKernelGGL((ek_filter_fixed_mv_kernel<RHS, q, true, false>), dim3(grid), dim3(kWave), 0, s, P);
+        else hipLaunchKernelGGL((ek_filter_fixed_mv_kernel<RHS, q, false, false>), dim3(grid), dim3(kWave), 0, s, P);
+      } else {
+        rc = -2;
+      }
+      return;
+    }
     if constexpr (RHS::d * (q + 1) <= kRowsMaxD) {
       if (P.N < filter_rows_max_n()) {  // small ensemble: 16 lanes per trajectory
         const unsigned rgrid = rows_grid(P.N);
@@ -749,12 +864,26 @@ struct LaunchFilter {
     else hipLaunchKernelGGL((ek_filter_fixed_kernel<RHS, q, EK1, false>), dim3(grid), dim3(kWave), 0, s, P);
   }
 };
-struct LaunchSmooth {
+using LaunchFilter = LaunchFilterT<true>;
+using LaunchDense = LaunchDenseT<true>;
+using LaunchSample = LaunchSampleT<true>;
+template <bool WITH_MV = true>
+struct LaunchSmoothT {
   const SmoothParams& P;
   hipStream_t s;
+  int rc = 0;
   template <int d, int q>
   void operator()() {
     constexpr int TPB = kWave / SmoothTeam<d * (q + 1)>::lanes;
+    if (P.mv) {  // MV models: the row-team smoother at every ensemble size (the lane and broadcast smoothers carry one diffusion)
+      if constexpr (WITH_MV && d * (q + 1) <= 32) {
+        note_kernel("odef::rts_smooth_mv_kernel<%d, %d>", d, q);
+        hipLaunchKernelGGL((rts_smooth_mv_kernel<d, q>), dim3((unsigned)((P.N + TPB - 1) / TPB)), dim3(kWave), 0, s, P);
+      } else {
+        rc = -2;
+      }
+      return;
+    }
     // Small state AND a large ensemble: one lane per trajectory.  A small ensemble does not fill the chip that
     // way (N / 64 wavefronts for 1 024 SIMDs); the row-per-lane team kernel gives TPB x fewer trajectories per
     // wavefront, i.e. more wavefronts, and wins below kSmoothLaneMinN.
@@ -788,26 +917,31 @@ struct LaunchSmooth {
   }
 };
 
-// The launchers above with the signatures of a FieldLaunch table (launch.h); ONLYQ / ONLYEK1 as for dispatch_order
-template <class RHS, int ONLYQ = 0, bool ONLYEK1 = false>
+using LaunchSmooth = LaunchSmoothT<true>;
+
+// The launchers above with the signatures of a FieldLaunch table (launch.h); ONLYQ / ONLYEK1 as for dispatch_order.
+// WITH_MV: with the kernels of the MV diffusion models (a run-time compiled field builds them only for an MV context, jit.hip)
+template <class RHS, int ONLYQ = 0, bool ONLYEK1 = false, bool WITH_MV = true>
 int lane_filter(int q, int ek1, const FilterParams& P, hipStream_t s, int adaptive, double*, size_t, long*) {
-  LaunchFilter f{P, adaptive, s};
-  return dispatch_order<RHS, ONLYQ, ONLYEK1>(q, ek1, f);
+  LaunchFilterT<WITH_MV> f{P, adaptive, s};
+  const int rc = dispatch_order<RHS, ONLYQ, ONLYEK1>(q, ek1, f);
+  return rc ? rc : f.rc;
 }
-template <int d, int ONLYQ = 0>
+template <int d, int ONLYQ = 0, bool WITH_MV = true>
 int lane_smooth(int q, const SmoothParams& P, double*, hipStream_t s) {
-  LaunchSmooth f{P, s};
-  return dispatch_smooth_order<d, ONLYQ>(q, f);
-}
-template <int d, int ONLYQ = 0>
-int lane_dense(int q, const DenseParams& P, double*, hipStream_t s) {
-  LaunchDense f{P, s};
+  LaunchSmoothT<WITH_MV> f{P, s};
   const int rc = dispatch_smooth_order<d, ONLYQ>(q, f);
   return rc ? rc : f.rc;
 }
-template <int d, int ONLYQ = 0>
+template <int d, int ONLYQ = 0, bool WITH_MV = true>
+int lane_dense(int q, const DenseParams& P, double*, hipStream_t s) {
+  LaunchDenseT<WITH_MV> f{P, s};
+  const int rc = dispatch_smooth_order<d, ONLYQ>(q, f);
+  return rc ? rc : f.rc;
+}
+template <int d, int ONLYQ = 0, bool WITH_MV = true>
 int lane_sample(int q, const SampleParams& P, double*, hipStream_t s) {
-  LaunchSample f{P, s};
+  LaunchSampleT<WITH_MV> f{P, s};
   const int rc = dispatch_smooth_order<d, ONLYQ>(q, f);
   return rc ? rc : f.rc;
 }

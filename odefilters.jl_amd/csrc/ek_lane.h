@@ -128,11 +128,21 @@ struct RowLoad {
 };
 #endif
 
+// The diffusion record of one save: one value (scalar models, `diff` [n_save][N]) or d (MV models, [n_save][d][N]).
+__device__ inline void put_diff(RowStore& sd, double v) { sd.put(v); }
+template <int d>
+__device__ inline void put_diff(RowStore& sd, const SigV<d>& v) {
+#pragma unroll
+  for (int a = 0; a < d; ++a) sd.put(v.v[a]);
+}
+template <class G> constexpr int diff_width = 1;
+template <int d> constexpr int diff_width<SigV<d>> = d;
+
 // Stores one saved record of one trajectory.  `i0` (first trajectory of the wavefront) and
 // `slot` are wave-uniform, `lane` is the lane index.
-template <int D, int TRI>
+template <int D, int TRI, class Diff = double>
 __device__ inline void store_state(const FilterParams& P, long slot, long i0, unsigned lane, const double (&m)[D],
-                                   const double (&C)[TRI], double diffusion) {
+                                   const double (&C)[TRI], Diff diffusion) {
   const size_t N = (size_t)P.N;
   RowStore sm(P.mean + ((size_t)slot * D * N + i0), N, D, lane);
 #pragma unroll
@@ -140,8 +150,9 @@ __device__ inline void store_state(const FilterParams& P, long slot, long i0, un
   RowStore sc(P.cov + ((size_t)slot * TRI * N + i0), N, TRI, lane);
 #pragma unroll
   for (int k = 0; k < TRI; ++k) sc.put(C[k]);
-  RowStore sd(P.diff + ((size_t)slot * N + i0), N, 1, lane);
-  sd.put(diffusion);
+  constexpr int ND = diff_width<Diff>;
+  RowStore sd(P.diff + ((size_t)slot * ND * N + i0), N, ND, lane);
+  put_diff(sd, diffusion);
 }
 
 // Sink of EKStep::run that stores each value of the step's record as soon as it exists.
@@ -160,11 +171,13 @@ struct RecordSink {
 // moves); for a SMALL ensemble (one wave on a few SIMDs, memory system idle) it is exposed latency: at 4 096
 // trajectories 6.2 ms with the burst, 5.8 ms lagged (4.5 ms without stores at all; the rest is the instructions of
 // the stores themselves).  `next` is a compile-time constant at every call site once run() is unrolled.
-template <int D, int TRI>
+// (Diff: double, or SigV<d> for the MV models, whose d diffusions are the last d stores)
+template <int D, int TRI, class Diff = double>
 struct LaggedSink {
+  static constexpr int ND = diff_width<Diff>;
   const double (&m)[D];
   const double (&C)[TRI];
-  double diffusion;
+  Diff diffusion;
   RowStore sm, sc, sd;
   int next;
   __device__ inline void mean(double) {}
@@ -172,12 +185,12 @@ struct LaggedSink {
   __device__ inline void tick() {
     if (next < D) sm.put(m[next]);
     else if (next < D + TRI) sc.put(C[next - D]);
-    else if (next == D + TRI) sd.put(diffusion);
+    else if (next < D + TRI + ND) sd.put(sig_comp(diffusion, next - D - TRI));
     ++next;
   }
   __device__ inline void flush() {
 #pragma unroll
-    for (int k = 0; k <= D + TRI; ++k)
+    for (int k = 0; k < D + TRI + ND; ++k)
       if (k >= next) tick();
   }
 };
@@ -193,10 +206,11 @@ __device__ inline bool all_finite(const double (&m)[D]) {
 // EVERY: every step is saved (compile-time: with a run-time flag each of the 91 stores of a step sat behind
 // its own branch, which cost 10 % in instructions and scheduling).
 // LAG (with EVERY): the record of step n is stored while step n + 1 runs (LaggedSink) -- for small ensembles.
-template <class RHS, int q, bool IS_EK1, bool EVERY, bool LAG = false>
+// MV: the diagonal diffusion models (EKStep), d diffusions per record.
+template <class RHS, int q, bool IS_EK1, bool EVERY, bool LAG = false, bool MV = false>
 __device__ inline void filter_fixed_lane(const FilterParams& P, long i0, unsigned lane) {
   const long i = i0 + lane;
-  using S = EKStep<RHS, q, IS_EK1>;
+  using S = EKStep<RHS, q, IS_EK1, MV>;
   constexpr int d = S::d, D = S::D, TRI = S::TRI, np = RHS::np;
   double pl[np > 0 ? np : 1];
 #pragma unroll
@@ -209,23 +223,27 @@ __device__ inline void filter_fixed_lane(const FilterParams& P, long i0, unsigne
   taylor_init<RHS, q>(u0, pl, m);
 #pragma unroll
   for (int k = 0; k < TRI; ++k) C[k] = 0.0;
-  if constexpr (EVERY && !LAG) store_state<D, TRI>(P, 0, i0, lane, m, C, 0.0);
+  using Diff = SigT<d, MV>;
+  constexpr int ND = MV ? d : 1;
+  Diff gdiff{};
+  if constexpr (!MV) gdiff = 0.0;
+  if constexpr (EVERY && !LAG) store_state<D, TRI>(P, 0, i0, lane, m, C, gdiff);
 
-  double loglik = 0.0, gdiff = 0.0;
+  double loglik = 0.0;
   LogDetAcc lda;  // log det S of the steps, multiplied up (ek_math.h): det S = (prod |R_kk|)^2
   lda.init();
   int chol_fix = 0;
   for (long n = 0; n < P.nsteps; ++n) {
     const GlobalTab tab{P.ptab + (size_t)uniform_load(P.tab_idx + n) * kTabStride};  // wave-uniform, scalar loads
     double m2[D], C2[TRI], es[d];
-    StepAux aux;
+    std::conditional_t<MV, StepAuxMV<d>, StepAux> aux;
     aux.chol_fix = 0;
     const size_t Nn = (size_t)P.N;
     if constexpr (EVERY && LAG) {  // record n = the inputs of this step
-      LaggedSink<D, TRI> sink{m, C, gdiff,
-                              RowStore(P.mean + ((size_t)n * D * Nn + i0), Nn, D, lane),
-                              RowStore(P.cov + ((size_t)n * TRI * Nn + i0), Nn, TRI, lane),
-                              RowStore(P.diff + ((size_t)n * Nn + i0), Nn, 1, lane), 0};
+      LaggedSink<D, TRI, Diff> sink{m, C, gdiff,
+                                    RowStore(P.mean + ((size_t)n * D * Nn + i0), Nn, D, lane),
+                                    RowStore(P.cov + ((size_t)n * TRI * Nn + i0), Nn, TRI, lane),
+                                    RowStore(P.diff + ((size_t)n * ND * Nn + i0), Nn, ND, lane), 0};
       S::run(P.pc, pl, tab, P.fixed_diffusion, P.want_loglik != 0, (int)n, gdiff, m, C, m2, C2, es, aux, sink);
       sink.flush();
     } else if constexpr (EVERY) {
@@ -242,11 +260,12 @@ __device__ inline void filter_fixed_lane(const FilterParams& P, long i0, unsigne
     for (int k = 0; k < TRI; ++k) C[k] = C2[k];
     loglik += aux.loglik;
     if (P.want_loglik) lda.mul(aux.det);
-    gdiff = aux.sigma2_global;
+    if constexpr (MV) gdiff = aux.sig_global;
+    else gdiff = aux.sigma2_global;
     chol_fix += aux.chol_fix;
     if constexpr (EVERY && !LAG) {
-      RowStore sd(P.diff + ((size_t)(n + 1) * Nn + i0), Nn, 1, lane);
-      sd.put(gdiff);
+      RowStore sd(P.diff + ((size_t)(n + 1) * ND * Nn + i0), Nn, ND, lane);
+      put_diff(sd, gdiff);
     }
   }
   if constexpr (!EVERY) store_state<D, TRI>(P, 0, i0, lane, m, C, gdiff);
@@ -272,9 +291,9 @@ __device__ inline double precond_val(double h) {
 
 // Per-lane (non-uniform slot) record store / reload for the adaptive filter: plain global accesses with
 // per-lane addresses (a buffer descriptor built from a lane-varying slot would be waterfalled per store).
-template <int D, int TRI>
+template <int D, int TRI, class Diff = double>
 __device__ inline void store_state_scatter(const FilterParams& P, long slot, long i, const double (&m)[D],
-                                           const double (&C)[TRI], double diffusion, double t) {
+                                           const double (&C)[TRI], Diff diffusion, double t) {
   const size_t N = (size_t)P.N;
   double* pm = P.mean + ((size_t)slot * D * N + i);
 #pragma unroll
@@ -282,7 +301,9 @@ __device__ inline void store_state_scatter(const FilterParams& P, long slot, lon
   double* pcv = P.cov + ((size_t)slot * TRI * N + i);
 #pragma unroll
   for (int k = 0; k < TRI; ++k) { *pcv = C[k]; pcv += N; }
-  P.diff[(size_t)slot * N + i] = diffusion;
+  constexpr int ND = diff_width<Diff>;
+#pragma unroll
+  for (int a = 0; a < ND; ++a) P.diff[((size_t)slot * ND + a) * N + i] = sig_comp(diffusion, a);
   P.tsave[(size_t)slot * N + i] = t;
 }
 template <int D, int TRI>
@@ -307,10 +328,10 @@ __device__ inline void load_state_scatter(const FilterParams& P, long slot, long
 // (src/smoothing.jl:13-16); the host mirror drops those records when it builds sol.t / sol.u.  Storing accepted
 // steps only (slot = accepted count, different per lane after the first rejection) splits every store
 // instruction over 3-4 rows and ran 3x slower (1.1 TB/s of scattered 8-byte writes).
-template <class RHS, int q, bool IS_EK1>
+template <class RHS, int q, bool IS_EK1, bool MV = false>
 __device__ inline void filter_adaptive_lane(const FilterParams& P, long i0, unsigned lane) {
   const long i = i0 + lane;
-  using S = EKStep<RHS, q, IS_EK1>;
+  using S = EKStep<RHS, q, IS_EK1, MV>;
   constexpr int d = S::d, D = S::D, TRI = S::TRI, np = RHS::np, NB = q + 1;
   double pl[np > 0 ? np : 1];
 #pragma unroll
@@ -323,14 +344,16 @@ __device__ inline void filter_adaptive_lane(const FilterParams& P, long i0, unsi
   taylor_init<RHS, q>(u0, pl, m);
 #pragma unroll
   for (int k = 0; k < TRI; ++k) C[k] = 0.0;
-  store_state_scatter<D, TRI>(P, 0, i, m, C, 0.0, P.t0);
+  SigT<d, MV> gdiff{};
+  if constexpr (!MV) gdiff = 0.0;
+  store_state_scatter<D, TRI>(P, 0, i, m, C, gdiff, P.t0);
 
   double ucur[d];
 #pragma unroll
   for (int a = 0; a < d; ++a) ucur[a] = u0[a];
   const Controller& ct = P.ctrl;
   double t = P.t0, h = P.dt0, qold = ct.qoldinit, q11 = 1.0, log_qold = log(ct.qoldinit), log_eest = 0.0;
-  double loglik = 0.0, gdiff = 0.0;
+  double loglik = 0.0;
   LogDetAcc lda;
   lda.init();
   int naccept = 0, nreject = 0, nsaved = 1, ret = 0;
@@ -346,7 +369,7 @@ __device__ inline void filter_adaptive_lane(const FilterParams& P, long i0, unsi
     precond_table_fast<q, NB, true>(h, tabv);  // no division, no libm pow: rebuilt at every attempted step
     const LocalTab tab{tabv};
     double es[d];
-    StepAux aux;
+    std::conditional_t<MV, StepAuxMV<d>, StepAux> aux;
     aux.chol_fix = 0;
     {
       double m2[D], C2[TRI];
@@ -397,7 +420,8 @@ __device__ inline void filter_adaptive_lane(const FilterParams& P, long i0, unsi
       double tn = t + h;
       if (fabs(tn - P.t1) < 100.0 * 2.220446049250313e-16 * fmax(fabs(tn), fabs(P.t1))) tn = P.t1;
       t = tn;
-      gdiff = aux.sigma2_global;
+      if constexpr (MV) gdiff = aux.sig_global;
+      else gdiff = aux.sigma2_global;
       ++naccept;
       h = h / qq;
     } else {
@@ -454,6 +478,7 @@ struct SmoothParams {
   // (factorisation, sweeps, mean, G M G', the smoothed record) runs on chip in rts_smooth_sweeps_kernel, launched behind it
   int split_mode;
   long split_sc, split_sa;  // split_sa: the record of this pair of launches; split_sc == 1: Y' = A X is formed by the on-chip kernel from the record (no hand-over through the workspace)
+  int mv;  // diff holds d diffusions per record (the MV diffusion models; row-team smoother only, rts_smooth_mv_kernel)
 };
 
 }  // namespace odef

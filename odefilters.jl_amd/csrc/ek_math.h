@@ -12,6 +12,7 @@
 #pragma once
 #include "odef_platform.h"
 #include "rhs.h"
+#include <type_traits>
 
 // Scheduling fence: keeps the instruction scheduler from hoisting every load of a fully unrolled loop
 // nest to the top (which costs hundreds of registers).  No code is emitted.
@@ -296,8 +297,35 @@ struct NoTick {
 // `tick()` is called at regular points of the arithmetic; the lagged record sink of the filter (ek_lane.h) uses it to
 // spread the stores of the previous record over the step.
 // `T`: the scalar type of the covariance (double in every kernel; a host emulation of a multi-lane mapping may pass a vector type).
-template <int d, int NB, class T, class Tick = NoTick>
-__device__ inline void predict_cov_inplace(const PriorConsts& pc, T (&X)[d * NB * (d * NB + 1) / 2], T sigma2,
+// Diffusion of the MV ("multivariate") models :dynamicMV / :fixedMV (src/diffusions.jl:83-153): one value per state
+// component, Sigma = diag(sigma_1 .. sigma_d), applied as kron(I_{q+1}, Sigma) (src/ProbNumDiffEq.jl:38).  Since Q = Qt (x) I_d,
+// X_A_Xt(Q, sqrt.(kron(I, Sigma))) multiplies the (J a, K a) entries of Q by sigma_a and leaves the zero (a != b) ones zero.
+template <int d>
+struct SigV {
+  double v[d];
+};
+template <class S>
+__host__ __device__ inline S sig_comp(const S& s, int) { return s; }  // the scalar models: the same sigma^2 for every component
+template <int d>
+__host__ __device__ inline double sig_comp(const SigV<d>& s, int a) { return s.v[a]; }
+template <int d, bool MV>
+using SigT = std::conditional_t<MV, SigV<d>, double>;
+// diffusion record of save slot `sd` of trajectory i: [n_save][N] (scalar models) or [n_save][d][N] (MV models)
+template <int d, bool MV>
+__device__ inline SigT<d, MV> load_sig(const double* __restrict__ diff, size_t sd, size_t N, size_t i) {
+  if constexpr (MV) {
+    SigV<d> s;
+#pragma unroll
+    for (int a = 0; a < d; ++a) s.v[a] = diff[(sd * d + a) * N + i];
+    return s;
+  } else {
+    return diff[sd * N + i];
+  }
+}
+
+// `sigma2`: a scalar (T) or an MV diagonal (SigV<d>)
+template <int d, int NB, class T, class Tick = NoTick, class Sig = T>
+__device__ inline void predict_cov_inplace(const PriorConsts& pc, T (&X)[d * NB * (d * NB + 1) / 2], Sig sigma2,
                                            Tick tick = Tick{}) {
   constexpr int D = d * NB;
 #pragma unroll
@@ -343,7 +371,7 @@ __device__ inline void predict_cov_inplace(const PriorConsts& pc, T (&X)[d * NB 
 #pragma unroll
     for (int K = 0; K <= J; ++K)
 #pragma unroll
-      for (int a = 0; a < d; ++a) X[tri(J * d + a, K * d + a)] += sigma2 * pc.Qt[J][K];
+      for (int a = 0; a < d; ++a) X[tri(J * d + a, K * d + a)] += sig_comp(sigma2, a) * pc.Qt[J][K];
 }
 
 // Cholesky of a small SPD matrix, lower factor L and the reciprocals of its diagonal.
@@ -385,8 +413,17 @@ __host__ __device__ inline double static_diffusion_update(int mode, int success_
   return (beta + 0.5 * res_sum_t) / (alpha + n_obs * d / 2.0 + 1.0);
 }
 
-template <class RHS, int q, bool IS_EK1>
+// ... and of an MV step: the local and global diffusion per state component (cache.local_diffusion / global_diffusion)
+template <int d>
+struct StepAuxMV : StepAux {
+  SigV<d> sig_local, sig_global;
+};
+
+// MV: the diagonal diffusion models (EK0 only, src/diffusions.jl:96, :125); `fixed_diffusion` is then the C ABI's
+// odef_diffusion value 3 (:dynamicMV) or 4 (:fixedMV), `prev_global` a SigV<d> and `aux` a StepAuxMV<d>.
+template <class RHS, int q, bool IS_EK1, bool MV = false>
 struct EKStep {
+  static_assert(!(MV && IS_EK1), "MV diffusion models require EK0");
   static constexpr int d = RHS::d;
   static constexpr int NB = q + 1;
   static constexpr int D = d * NB;
@@ -408,11 +445,11 @@ struct EKStep {
   // `sink.mean(v)` / `sink.cov(v)` receive the un-preconditioned results in storage order as soon as each
   // value exists; `sink.tick()` is called at ~110 points spread evenly over the arithmetic of the step (never
   // inside a run-time branch), so that a sink can spread its stores over the step (LaggedSink, ek_lane.h).
-  template <class Sink, class Tab>
+  template <class Sink, class Tab, class Prev = double, class Aux = StepAux>
   __device__ static inline void run(const PriorConsts& pc, const double* __restrict__ p, const Tab& tab,
-                                    int fixed_diffusion, bool want_loglik, int success_iter, double prev_global,
+                                    int fixed_diffusion, bool want_loglik, int success_iter, Prev prev_global,
                                     const double (&m)[D], const double (&C)[TRI], double (&m_out)[D],
-                                    double (&C_out)[TRI], double (&err_scale)[d], StepAux& aux, Sink& sink) {
+                                    double (&C_out)[TRI], double (&err_scale)[d], Aux& aux, Sink& sink) {
     // x~ = P x  (src/perform_step.jl:36-38)
     double mt[D];
 #pragma unroll
@@ -491,8 +528,23 @@ struct EKStep {
     }
 
     sink.tick();
-    double sigma2_pred = 1.0;  // diffusion used inside predict_cov!
-    if (!fixed_diffusion) {
+    SigT<d, MV> sigma2_pred;  // diffusion used inside predict_cov!
+    if constexpr (MV) {
+      // MVDynamicDiffusion (src/diffusions.jl:83-112): sigma_a = max(z_a^2 / (H Q H')_11, eps) -- H Q H' is a multiple of I for
+      // EK0 and the reference takes its first entry.  MVFixedDiffusion predicts with the unscaled Q (sigma = 1) and calibrates
+      // after the measurement, below.
+      const bool dyn = fixed_diffusion == 3;
+#pragma unroll
+      for (int a = 0; a < d; ++a) sigma2_pred.v[a] = dyn ? fmax(z[a] * z[a] / W[0][0], 2.220446049250313e-16) : 1.0;
+      if (dyn) {
+        aux.sig_local = sigma2_pred;
+        aux.sig_global = sigma2_pred;
+      }
+      aux.sigma2_local = aux.sigma2_global = 0.0;
+    } else {
+      sigma2_pred = 1.0;
+    }
+    if constexpr (!MV) if (!fixed_diffusion) {
       // DynamicDiffusion (src/diffusions.jl:72-80): sigma^2 = z' (H Q H')^-1 z / d = |Lw^-1 z|^2 / d
       double Lw[d][d], Lwi[d];
       chol_small<d>(W, Lw, Lwi);
@@ -612,7 +664,19 @@ struct EKStep {
     }
     aux.det = (d <= 4) ? fabs(detprod) : 1.0;
 
-    if (fixed_diffusion) {
+    if constexpr (MV) {
+      if (fixed_diffusion == 4) {
+        // MVFixedDiffusion (src/diffusions.jl:115-153): sigma_a(t) = z_a^2 / S_11 with the FIRST diagonal entry of S = R'R for
+        // every component; global: running mean over the accepted steps, as FixedDiffusion
+        const double s11 = R[0][0] * R[0][0];
+#pragma unroll
+        for (int a = 0; a < d; ++a) {
+          const double st = z[a] * z[a] / s11;
+          aux.sig_local.v[a] = st;
+          aux.sig_global.v[a] = static_diffusion_update<d>(1, success_iter, prev_global.v[a], st);
+        }
+      }
+    } else if (fixed_diffusion) {
       // FixedDiffusion (src/diffusions.jl:11-36): running mean of z' S^-1 z / d;  MAPFixedDiffusion (:46-68)
       const double diffusion_t = zSz / d;
       aux.sigma2_local = diffusion_t;
@@ -622,7 +686,10 @@ struct EKStep {
     // error estimate scale (src/perform_step.jl:148-158)
     sink.tick();
 #pragma unroll
-    for (int r = 0; r < d; ++r) err_scale[r] = sqrt(aux.sigma2_local * W[r][r]);
+    for (int r = 0; r < d; ++r) {
+      if constexpr (MV) err_scale[r] = sqrt(aux.sig_local.v[r] * W[r][r]);
+      else err_scale[r] = sqrt(aux.sigma2_local * W[r][r]);
+    }
     sink.tick();
 
     // update! (src/filtering.jl:79-91): rows of L1 times Q, Q = H_1 ... H_d.  Only d + 1 combinations of the columns of Q

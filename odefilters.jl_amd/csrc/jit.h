@@ -16,6 +16,7 @@ bool jit_lookup(int rhs_id, int* d, int* np);
 // into a host + device shared object around the field (seconds; minutes on the workgroup-per-trajectory kernels).
 // abi_stamp: team_abi_stamp() of the library
 struct FieldLaunch;
-const FieldLaunch* jit_field(int rhs_id, int q, int ek1, unsigned long abi_stamp, std::string& err);
+// mv: the MV diffusion models' kernels are built (only) for an MV context -- a module of its own, the key includes it
+const FieldLaunch* jit_field(int rhs_id, int q, int ek1, int mv, unsigned long abi_stamp, std::string& err);
 
 }  // namespace odef

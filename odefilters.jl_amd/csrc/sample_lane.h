@@ -34,6 +34,7 @@ struct SampleParams {
   const double* rec_t;  // fixed solves: [n_rec] record times (adaptive solves: tsave / nsaved)
   long n_rec;
   double* samples;      // [n_save][D][n_samples][N]
+  int mv;               // diff holds d diffusions per record (the MV diffusion models)
 };
 
 __device__ inline unsigned long long splitmix64_dev(unsigned long long x) {
@@ -73,7 +74,7 @@ __device__ inline void draw_packed(const double (&m)[D], double (&C)[D * (D + 1)
   }
 }
 
-template <int d, int q>
+template <int d, int q, bool MV = false>
 __device__ inline void sample_lane(const SampleParams& P, long i, long j, const LaneMem& xl, long n_hi) {
   constexpr int NB = q + 1, D = d * NB, TRI = D * (D + 1) / 2;
   const size_t N = (size_t)P.N, NS = (size_t)P.n_samples;
@@ -133,7 +134,7 @@ __device__ inline void sample_lane(const SampleParams& P, long i, long j, const 
       sd = lo < nrec - 1 ? lo : nrec - 1;
       if (sd < 1) sd = nrec > 1 ? 1 : 0;
     }
-    const double sigma2 = P.diff[(size_t)sd * N + i];
+    const auto sigma2 = load_sig<d, MV>(P.diff, (size_t)sd, N, (size_t)i);
     // all loads of the step first, arithmetic afterwards (see smooth_lane_v2)
     double mt[D], B[TRI], Cs[TRI], msn[D], mc[D];
     {

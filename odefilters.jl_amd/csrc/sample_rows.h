@@ -44,7 +44,7 @@ _Pragma("unroll")
   )
 }
 
-template <int d, int q, int TEAM>
+template <int d, int q, int TEAM, bool MV = false>
 __device__ inline void sample_rows_lane(const SampleParams& P, long i, long j, int tid, double* __restrict__ ws, RowState<d*(q + 1)>* st) {
   constexpr int NB = q + 1, D = d * NB, TRI = D * (D + 1) / 2;
   const size_t N = (size_t)P.N, NS = (size_t)P.n_samples;
@@ -118,7 +118,7 @@ _Pragma("unroll")
       sd = lo < nrec - 1 ? lo : nrec - 1;
       if (sd < 1) sd = nrec > 1 ? 1 : 0;
     }
-    const double sigma2 = P.diff[(size_t)sd * N + i];
+    const auto sigma2 = load_sig<d, MV>(P.diff, (size_t)sd, N, (size_t)i);
     // the filter state of slot s, preconditioned; the later sample (in L.ms) is the "smoothed next state" with zero covariance
     ODEF_ROWS_PHASE(
       if (r < D) {

@@ -121,10 +121,10 @@ __device__ inline void congruence_At_inplace(const PriorConsts& pc, double (&X)[
 //        msn = P m^s_+, Cs = P S^s_+ P (packed; destroyed), sigma2, pij = diag of P^-1 per derivative block
 //   out: ms_out (un-preconditioned smoothed mean), sink(k, v) for every packed entry k of the
 //        un-preconditioned smoothed covariance, in storage order
-template <int d, int NB, class CovSink>
+template <int d, int NB, class CovSink, class Sig = double>
 __device__ inline void rts_step_core(const PriorConsts& pc, const double (&pij)[NB], const double (&mt)[d * NB],
                                      double (&B)[d * NB * (d * NB + 1) / 2], double (&Cs)[d * NB * (d * NB + 1) / 2],
-                                     const double (&msn)[d * NB], double sigma2, const LaneMem& xl,
+                                     const double (&msn)[d * NB], Sig sigma2, const LaneMem& xl,
                                      double (&ms_out)[d * NB], CovSink& sink) {
   constexpr int D = d * NB, TRI = D * (D + 1) / 2;
   // predict (src/smoothing.jl:38)

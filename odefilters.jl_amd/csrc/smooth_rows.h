@@ -98,8 +98,9 @@ _Pragma("unroll")
 // rows_predict_phase:  L.yr / YL = row of Y = S A', L.mpred = (A m~)_r, L.lr = row r of B = A S A' + sigma2 Q (preconditioned),
 //                      MM = row of M = P S^s_+ P - B, VDL = P m^s_+ - m^-
 // rows_gain_phase:     B = L D L', G = Y B^-1, L.ms <- P^-1 (m~ + G delta), L.csr <- full row r of P^-1 (S + G M G') P^-1
-template <int d, int q, int TEAM>
-__device__ inline void rows_predict_phase(const PriorConsts& pc, const double (&pjv)[q + 1], double sigma2, int tid, double* __restrict__ ws,
+// `sigma2`: a scalar or the MV diagonal (SigV<d>, ek_math.h); lane r takes the diffusion of its component r % d
+template <int d, int q, int TEAM, class Sig = double>
+__device__ inline void rows_predict_phase(const PriorConsts& pc, const double (&pjv)[q + 1], Sig sigma2, int tid, double* __restrict__ ws,
                                           RowState<d*(q + 1)>* st) {
   constexpr int NB = q + 1, D = d * NB;
   using W = RowsWs<d, NB>;
@@ -144,7 +145,7 @@ _Pragma("unroll")
 _Pragma("unroll")
         for (int j = 0; j < NB; ++j)
           if (j > J) acc += L.atr[j] * YL[(j * d + a) * LD + c];
-        if (a == c % d) acc += sigma2 * L.qtr[c / d];
+        if (a == c % d) acc += sig_comp(sigma2, a) * L.qtr[c / d];
         L.lr[c] = acc;
         MM[r * LD + c] = L.csr[c] * (L.pj * pjv[c / d]) - acc;  // M = P S^s_+ P - S^-
         ODEF_SCHED_FENCE();
@@ -249,7 +250,8 @@ _Pragma("unroll")
 }
 
 // whole backward pass of trajectory i.  `st`: one RowState (device) / TEAM RowStates (host emulation).
-template <int d, int q, int TEAM>
+// MV: d diffusions per record (the MV diffusion models).
+template <int d, int q, int TEAM, bool MV = false>
 __device__ inline void smooth_rows_lane(const SmoothParams& P, long i, int tid, double* __restrict__ ws, RowState<d*(q + 1)>* st) {
   constexpr int NB = q + 1, D = d * NB, TRI = D * (D + 1) / 2;
   using W = RowsWs<d, NB>;
@@ -329,7 +331,7 @@ _Pragma("unroll")
       )
       continue;
     }
-    const double sigma2 = P.diff[(size_t)(s + 1) * N + i];
+    const auto sigma2 = load_sig<d, MV>(P.diff, (size_t)(s + 1), N, (size_t)i);
     // phase 1: load row r and precondition it
     ODEF_ROWS_PHASE(
       if (r < D) {

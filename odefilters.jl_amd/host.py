@@ -24,7 +24,9 @@ LIB_PATH = os.environ.get("ODEFILTER_HIP_LIB") or os.path.join(_HERE, "lib", "li
 
 # ---- enums (include/odefilter.h) ---------------------------------------------------------
 EK0_ID, EK1_ID = 0, 1
-DIFFUSION = {"dynamic": 0, "fixed": 1, "fixedMAP": 2}
+DIFFUSION = {"dynamic": 0, "fixed": 1, "fixedMAP": 2, "dynamicMV": 3, "fixedMV": 4}
+# the diagonal ("multivariate") models: one diffusion per state component, EK0 on the lane kernels only (include/odefilter.h)
+MV_DIFFUSIONS = ("dynamicMV", "fixedMV")
 RHS = {"fhn": 0, "lorenz63": 1, "lotka_volterra": 2, "vanderpol": 3, "linear": 4, "pleiades": 5, "lorenz96": 6}
 RHS_DIMS = {"fhn": (2, 3), "lorenz63": (3, 3), "lotka_volterra": (2, 4), "vanderpol": (2, 1), "linear": (2, 2),
             "pleiades": (28, 0), "lorenz96": (16, 1)}
@@ -150,6 +152,7 @@ class DeviceGroup:
         cfg.save_mode = SAVE_EVERYSTEP if (save_everystep or smooth) else SAVE_FINAL
         cfg.device, cfg.want_loglik, cfg.n_traj = -1, int(want_loglik), n_traj
         self.d, self.D, self.N, self.G = d, d * (order + 1), n_traj, n_devices
+        self.TRI, self.mv = self.D * (self.D + 1) // 2, diffusion in MV_DIFFUSIONS
         ids = (C.c_int32 * n_devices)(*device_ids) if device_ids is not None else None
         h = _vp()
         if self.lib.odef_group_create(C.byref(h), C.byref(cfg), n_devices, ids) != 0:
@@ -204,6 +207,30 @@ class DeviceGroup:
         self._chk(self.lib.odef_group_get_gathered(self._h, from_device, _as_dp(out), None, None))
         return out
 
+    def gather_field(self, f: int) -> np.ndarray:
+        """A per-save or per-trajectory field of the WHOLE ensemble, read shard by shard from the hosts of the shards and
+        joined along the trajectory axis: the layout of Context.get for one context of all N trajectories (the d-wide
+        DIFFUSION of the MV models included)."""
+        parts = []
+        for g in range(self.G):
+            c = self.lib.odef_group_ctx(self._h, g)
+            b = C.c_size_t()
+            if self.lib.odef_field_bytes(c, f, C.byref(b)) != 0:
+                raise OdefError(f"odef_field_bytes failed for field {f} of shard {g}")
+            dt = np.int32 if f in _INT_FIELDS else np.float64
+            out = np.empty(b.value // np.dtype(dt).itemsize, dtype=dt)
+            if self.lib.odef_get(c, f, out.ctypes.data_as(_vp), b.value) != 0:
+                raise OdefError(self.lib.odef_last_error(c).decode())
+            n = self.shard(g)[1]
+            if f in (F_MEAN, F_SMOOTH_MEAN):
+                out = out.reshape(-1, self.D, n)
+            elif f in (F_COV_TRIL, F_SMOOTH_COV_TRIL):
+                out = out.reshape(-1, self.TRI, n)
+            elif f == F_DIFFUSION:
+                out = out.reshape(-1, self.d, n) if self.mv else out.reshape(-1, n)
+            parts.append(out)
+        return np.concatenate(parts, axis=-1)
+
     def shard_kernel_ms(self, which=0):
         ms = []
         for g in range(self.G):
@@ -251,6 +278,7 @@ class Context:
         cfg.save_mode = SAVE_EVERYSTEP if (save_everystep or smooth) else SAVE_FINAL
         cfg.device, cfg.want_loglik, cfg.n_traj = device, int(want_loglik), n_traj
         self.cfg = cfg
+        self.mv = diffusion in MV_DIFFUSIONS
         self.d, self.q, self.N = d, order, n_traj
         self.D = d * (order + 1)
         self.TRI = self.D * (self.D + 1) // 2
@@ -374,7 +402,7 @@ class Context:
         if f in (F_COV_TRIL, F_SMOOTH_COV_TRIL):
             return out.reshape(ns, self.TRI, N)
         if f == F_DIFFUSION:
-            return out.reshape(ns, N)
+            return out.reshape(ns, self.d, N) if self.mv else out.reshape(ns, N)
         if f == F_T:
             return out.reshape(ns, N) if out.size == ns * N and out.size != ns else out
         if f == F_U0:
@@ -749,7 +777,10 @@ class EnsembleSolution:
 
     @property
     def diffusions(self) -> np.ndarray:
-        """[N, n_save-1]: entry k = diffusion of step t[k] -> t[k+1] (src/integrator_utils.jl:44)."""
+        """[N, n_save-1]: entry k = diffusion of step t[k] -> t[k+1] (src/integrator_utils.jl:44); the MV models:
+        [N, n_save-1, d], the diagonal of that diffusion."""
+        if self.ctx.mv:
+            return self._compact(self._get(F_DIFFUSION).transpose(2, 0, 1))[:, 1:]
         return self._compact(self._get(F_DIFFUSION).T)[:, 1:]
 
     @property
@@ -807,7 +838,9 @@ def solve(prob, alg, ensemblealg: EnsembleHIP = EnsembleHIP(), *, trajectories: 
     if alg.prior != "ibm":
         raise OdefError("Only the ibm prior is implemented so far")  # src/caches.jl:69
     if alg.diffusionmodel not in DIFFUSION:
-        raise OdefError(f"diffusionmodel {alg.diffusionmodel!r} is not on the device path; use 'dynamic', 'fixed' or 'fixedMAP'")
+        raise OdefError(f"diffusionmodel {alg.diffusionmodel!r} is not on the device path; use one of {sorted(DIFFUSION)}")
+    if alg.diffusionmodel in MV_DIFFUSIONS and alg._id != EK0_ID:
+        raise OdefError("MV diffusion models require EK0")  # src/diffusions.jl:96, :125
     if not adaptive and dt is None and tstops is None:
         # test/errors.jl:17-19
         raise OdefError("Fixed timestep methods require a choice of dt or choosing the tstops")
