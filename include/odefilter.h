@@ -22,6 +22,8 @@
  *                                   + PI controller (exponents src/alg_utils.jl:23-24; loop is OrdinaryDiffEq's)
  *   odef_smooth                     postamble! -> smooth_all! -> smooth!         src/integrator_utils.jl:2-30,
  *                                                                                src/smoothing.jl:4-63
+ *   ODEF_IEKS contexts              IEKS, solve_ieks: odef_solve_fixed + odef_smooth, repeated  src/ieks.jl:2-61
+ *                                   measure! with J = f.jac(linearize_at(t).mu)  src/perform_step.jl:111-113
  *   odef_dense_output               sol(t), GaussianODEFilterPosterior            src/solution.jl:165-214
  *   odef_sample                     sample_states / sample                        src/solution_sampling.jl:15-62
  *   odef_dense_sample               dense_sample_states / dense_sample            src/solution_sampling.jl:63-75
@@ -55,6 +57,12 @@
  *   NSAVED      int32 [N]          number of valid saves of a trajectory (adaptive)
  *   RETCODE     int32 [N]          odef_retcode
  *   SMOOTH_MEAN / SMOOTH_COV_TRIL  as MEAN / COV_TRIL after odef_smooth
+ *   LINEARIZE_AT [n_save][d][N]    IEKS only: the u part of a mean per save; step s -> s+1 reads row s+1, row 0 is unused.
+ *                                  Empty after odef_create, odef_set_problem* and odef_bind_device(ctx, F, NULL, 0): the step
+ *                                  is EK1.  Bound with odef_bind_device: caller memory, read only, at least n_t*d*N doubles
+ *                                  (IEKS(linearize_at = sol)).  Set by odef_smooth after a fixed-grid solve: rows 0..d-1 of
+ *                                  every SMOOTH_MEAN save, owned (a bound buffer is let go, never written), valid for that
+ *                                  grid only (alg.linearize_at = sol) -- odef_solve_fixed on another grid refuses it.
  * odef_get copies a field to host memory in exactly this layout.
  */
 #ifndef ODEFILTER_H
@@ -71,7 +79,13 @@ extern "C" {
 
 typedef struct odef_ctx odef_ctx;
 
-typedef enum { ODEF_EK0 = 0, ODEF_EK1 = 1 } odef_alg;
+/* EK0 / EK1 (src/algorithms.jl:23-51) and IEKS, the iterated extended Kalman smoother (src/ieks.jl:2-61): an EK1 context whose
+ * step evaluates the Jacobian at ODEF_F_LINEARIZE_AT when that field holds data (src/perform_step.jl:111-125), at the
+ * prediction (= EK1) when it is empty.  IEKS always smooths: odef_create refuses smooth = 0, the MV diffusion models and fields
+ * on the workgroup-per-trajectory kernels (Pleiades, Lorenz-96, run-time fields with d(q+1) > 20 or d > 10).  On an IEKS context
+ * odef_smooth after odef_solve_fixed sets ODEF_F_LINEARIZE_AT to the smoothed u on that grid, so that repeating
+ * odef_solve_fixed + odef_smooth is solve_ieks (src/ieks.jl:52-61); odef_solve_adaptive runs while the field is empty only. */
+typedef enum { ODEF_EK0 = 0, ODEF_EK1 = 1, ODEF_IEKS = 2 } odef_alg;
 /* diffusionmodel = :dynamic / :fixed / :fixedMAP / :dynamicMV / :fixedMV (src/caches.jl:89-96, src/diffusions.jl:11-36, 46-68,
  * 71-80, 83-153).  The MV ("multivariate") models calibrate one diffusion per state component, Sigma = diag(sigma_1..sigma_d);
  * they require EK0 and run on the lane kernels only (state dimension d(q+1) <= 20 and d <= 10: not Pleiades, not Lorenz-96),
@@ -118,6 +132,7 @@ typedef enum {
   ODEF_F_DENSE_MEAN = 14,      /* [n_q][D][N]   result of odef_dense_output */
   ODEF_F_DENSE_COV_TRIL = 15,  /* [n_q][TRI][N] */
   ODEF_F_SAMPLES = 16,         /* [n_save][D][n_samples][N] result of odef_sample */
+  ODEF_F_LINEARIZE_AT = 17,    /* [n_save][d][N] IEKS linearisation points (see odef_alg) */
   ODEF_F_COUNT_
 } odef_field;
 

@@ -7,7 +7,7 @@
 # it mirrors, call for call, what odefilters.jl_amd/host.py does over ctypes, which IS tested.
 module ODEFilterHIP
 
-using ProbNumDiffEq            # EK0, EK1 (src/algorithms.jl:23-51)
+using ProbNumDiffEq            # EK0, EK1 (src/algorithms.jl:23-51), IEKS (src/ieks.jl)
 import DiffEqBase
 using LinearAlgebra: Diagonal  # sol.diffusions of the MV models
 
@@ -27,6 +27,9 @@ const MV_DIFFUSIONS = (:dynamicMV, :fixedMV)
 const F_MEAN, F_COV_TRIL, F_DIFFUSION, F_T, F_LOGLIK, F_NACCEPT, F_NREJECT, F_NF, F_NJAC, F_NSAVED,
       F_RETCODE, F_SMOOTH_MEAN, F_SMOOTH_COV_TRIL = 0:12
 const F_SAMPLES = 16
+# IEKS (src/ieks.jl): the algorithm id and the field of linearisation points [n_save][d][N] (include/odefilter.h)
+const ODEF_IEKS = 2
+const F_LINEARIZE_AT = 17
 const RETCODES = (:Success, :MaxIters, :DtLessThanMin, :Unstable, :Unstable)
 
 """Ensemble algorithm: all trajectories of an `EnsembleProblem` on one GPU (`devices` empty / one entry) or sharded
@@ -87,9 +90,9 @@ end
 Returns the per-trajectory solution fields as arrays with the trajectory index FIRST (Julia column-major
 view of the device layout [n_save][D][N]): `mean[i, k, s]`.
 """
-function DiffEqBase.__solve(eprob::DiffEqBase.EnsembleProblem, alg::Union{EK0,EK1}, ealg::EnsembleHIP;
+function DiffEqBase.__solve(eprob::DiffEqBase.EnsembleProblem, alg::Union{EK0,EK1,IEKS}, ealg::EnsembleHIP;
                             trajectories::Int, u0s::Matrix{Float64}, dt=nothing, adaptive=true,
-                            abstol=1e-6, reltol=1e-3, max_steps=4096,
+                            abstol=1e-6, reltol=1e-3, max_steps=4096, ieks_iterations::Int=1,
                             nsamples::Int=0, sample_seed::UInt64=UInt64(0x5A3B1E), dense_sample_times=nothing, kwargs...)
     prob = eprob.prob
     d, N = size(u0s); @assert N == trajectories
@@ -97,8 +100,12 @@ function DiffEqBase.__solve(eprob::DiffEqBase.EnsembleProblem, alg::Union{EK0,EK
     p = collect(Float64, prob.p)
     !adaptive && dt === nothing && error("Fixed timestep methods require a choice of dt or choosing the tstops")
     mv = alg.diffusionmodel in MV_DIFFUSIONS
-    mv && alg isa EK1 && error("MV diffusion models require EK0")   # src/diffusions.jl:96, :125
-    cfg = Ref(OdefConfig(sizeof(OdefConfig), alg isa EK1 ? 1 : 0, q, DIFFUSIONS[alg.diffusionmodel],
+    mv && !(alg isa EK0) && error("MV diffusion models require EK0")   # src/diffusions.jl:96, :125
+    # IEKS: solve_ieks below; IEKS(linearize_at = sol) needs the linearisation points on the device (odef_bind_device of
+    # F_LINEARIZE_AT), which this host-array binding does not keep
+    alg isa IEKS && alg.linearize_at !== nothing && error("IEKS(linearize_at = sol): bind F_LINEARIZE_AT with odef_bind_device")
+    alg isa IEKS && adaptive && error("IEKS relinearisation runs on fixed grids")
+    cfg = Ref(OdefConfig(sizeof(OdefConfig), alg isa IEKS ? ODEF_IEKS : alg isa EK1 ? 1 : 0, q, DIFFUSIONS[alg.diffusionmodel],
                          alg.smooth ? 1 : 0, RHS_IDS[ealg.rhs], d, length(p), 1, 1, ealg.device, 1, N))
     h = Ref{Ptr{Cvoid}}(C_NULL)
     rc = ccall((:odef_create, LIB), Cint, (Ptr{Ptr{Cvoid}}, Ptr{OdefConfig}), h, cfg)
@@ -106,6 +113,7 @@ function DiffEqBase.__solve(eprob::DiffEqBase.EnsembleProblem, alg::Union{EK0,EK
     ctx = h[]
     try
         t0, t1 = Float64.(prob.tspan)
+        tgrid = Float64[]
         GC.@preserve u0s p check(ccall((:odef_set_problem, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cdouble),
                                        ctx, u0s, p, t0), ctx)
         if adaptive
@@ -113,11 +121,20 @@ function DiffEqBase.__solve(eprob::DiffEqBase.EnsembleProblem, alg::Union{EK0,EK
                         (Ptr{Cvoid}, Cdouble, Cdouble, Cdouble, Cdouble, Ptr{Cvoid}, Int64),
                         ctx, t1, abstol, reltol, dt === nothing ? 1e-3 * (t1 - t0) : dt, C_NULL, max_steps), ctx)
         else
-            tgrid = collect(t0:dt:t1); tgrid[end] < t1 && push!(tgrid, t1)   # OrdinaryDiffEq's clipped last step
+            tgrid = collect(Float64, t0:dt:t1); tgrid[end] < t1 && push!(tgrid, t1)   # OrdinaryDiffEq's clipped last step
             GC.@preserve tgrid check(ccall((:odef_solve_fixed, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Int64),
                                            ctx, tgrid, length(tgrid)), ctx)
         end
         alg.smooth && check(ccall((:odef_smooth, LIB), Cint, (Ptr{Cvoid},), ctx), ctx)
+        # solve_ieks (src/ieks.jl:52-61): odef_smooth has set F_LINEARIZE_AT to the smoothed u on this grid, so every
+        # further fixed-grid solve + smoother is the next iteration, on the device
+        if alg isa IEKS
+            for _ in 2:ieks_iterations
+                GC.@preserve tgrid check(ccall((:odef_solve_fixed, LIB), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Int64),
+                                               ctx, tgrid, length(tgrid)), ctx)
+                check(ccall((:odef_smooth, LIB), Cint, (Ptr{Cvoid},), ctx), ctx)
+            end
+        end
         ns = Int(ccall((:odef_n_save, LIB), Int64, (Ptr{Cvoid},), ctx))
         mean = fetch(ctx, alg.smooth ? F_SMOOTH_MEAN : F_MEAN, Float64, N, D, ns)
         cov  = fetch(ctx, alg.smooth ? F_SMOOTH_COV_TRIL : F_COV_TRIL, Float64, N, TRI, ns)
@@ -158,6 +175,17 @@ function DiffEqBase.__solve(eprob::DiffEqBase.EnsembleProblem, alg::Union{EK0,EK
     end
 end
 
+
+"""
+    solve_ieks(eprob, alg::IEKS, ealg::EnsembleHIP; iterations=10, kwargs...)
+
+`solve_ieks` (src/ieks.jl:52-61) on one IEKS context: the first iteration is EK1 (the field of linearisation points starts
+empty), each further one a fixed-grid solve linearised at the previous smoothed u plus the smoother, with no data leaving
+the device between iterations.  Returns what `__solve` returns for the last iteration.  Fixed grids only.
+"""
+solve_ieks(eprob::DiffEqBase.EnsembleProblem, alg::IEKS, ealg::EnsembleHIP; iterations::Int=10, kwargs...) =
+    DiffEqBase.__solve(eprob, IEKS(prior=alg.prior, order=alg.order, diffusionmodel=alg.diffusionmodel), ealg;
+                       adaptive=false, kwargs..., ieks_iterations=iterations)
 
 grouperr(g) = unsafe_string(ccall((:odef_group_last_error, LIB), Cstring, (Ptr{Cvoid},), g))
 gcheck(rc, g) = rc == 0 || error("libodefilter_hip: " * grouperr(g))

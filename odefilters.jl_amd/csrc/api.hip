@@ -79,6 +79,9 @@ struct odef_ctx {
   // complete_pending() does the wait + timing (pending: 1 = filter, 2 = smoother)
   bool defer = false;
   int pending = 0;
+  // IEKS: ODEF_F_LINEARIZE_AT was filled by odef_smooth (an owned buffer) from the fixed-grid solve on `lin_grid`
+  bool lin_set = false;
+  std::vector<double> lin_grid;
   std::string err;
 };
 
@@ -88,6 +91,18 @@ namespace {
 bool team_path(const odef_ctx* c) { return c->field->smooth_staged != nullptr; }
 // the MV diffusion models :dynamicMV / :fixedMV: d diffusions per record
 bool is_mv(int diffusion) { return diffusion == ODEF_DIFFUSION_DYNAMIC_MV || diffusion == ODEF_DIFFUSION_FIXED_MV; }
+// the EK1 step: EK1, and IEKS (whose step is EK1 while ODEF_F_LINEARIZE_AT is empty)
+bool is_ek1(int alg) { return alg == ODEF_EK1 || alg == ODEF_IEKS; }
+// IEKS: ODEF_F_LINEARIZE_AT is bound by the caller or set by odef_smooth (else the step is EK1)
+bool lin_active(const odef_ctx* c) { return c->f[ODEF_F_LINEARIZE_AT].bound || c->lin_set; }
+// empties ODEF_F_LINEARIZE_AT: a bound buffer is let go, an owned one is kept for the next odef_smooth
+void clear_lin(odef_ctx* c) {
+  Buf& b = c->f[ODEF_F_LINEARIZE_AT];
+  if (b.bound) b = Buf{};
+  b.valid = 0;
+  c->lin_set = false;
+  c->lin_grid.clear();
+}
 
 int fail(odef_ctx* c, const char* fmt, ...) {
   char buf[512];
@@ -158,6 +173,7 @@ size_t field_count(const odef_ctx* c, int field, long n_save) {
     case ODEF_F_DIFFUSION: return (size_t)n_save * (is_mv(c->cfg.diffusion) ? (size_t)c->d : 1) * N;
     case ODEF_F_T: return c->adaptive ? (size_t)n_save * N : (size_t)n_save;
     case ODEF_F_U0: return (size_t)c->d * N;
+    case ODEF_F_LINEARIZE_AT: return (size_t)n_save * c->d * N;
     case ODEF_F_DENSE_MEAN: return (size_t)c->n_q * c->D * N;
     case ODEF_F_DENSE_COV_TRIL: return (size_t)c->n_q * c->TRI * N;
     case ODEF_F_SAMPLES: return (size_t)n_save * c->D * (size_t)c->n_samples * N;
@@ -349,7 +365,7 @@ int odef_create(odef_ctx** out, const odef_config* cfg) {
   if (cfg->d != ri.d) return fail(nullptr, "odef_create: rhs %d has dimension %d, got d=%d", cfg->rhs_id, ri.d, cfg->d);
   if (cfg->n_params != ri.np) return fail(nullptr, "odef_create: rhs %d has %d parameters, got %d", cfg->rhs_id, ri.np, cfg->n_params);
   if (cfg->order < 1 || cfg->order > ODEF_MAX_ORDER) return fail(nullptr, "odef_create: order %d outside 1..%d", cfg->order, ODEF_MAX_ORDER);
-  if (cfg->alg != ODEF_EK0 && cfg->alg != ODEF_EK1) return fail(nullptr, "odef_create: unknown alg %d", cfg->alg);
+  if (cfg->alg != ODEF_EK0 && cfg->alg != ODEF_EK1 && cfg->alg != ODEF_IEKS) return fail(nullptr, "odef_create: unknown alg %d", cfg->alg);
   if (cfg->diffusion != ODEF_DIFFUSION_DYNAMIC && cfg->diffusion != ODEF_DIFFUSION_FIXED && cfg->diffusion != ODEF_DIFFUSION_FIXED_MAP &&
       !is_mv(cfg->diffusion))
     return fail(nullptr, "odef_create: unknown diffusion model %d", cfg->diffusion);
@@ -361,6 +377,16 @@ int odef_create(odef_ctx** out, const odef_config* cfg) {
                                                  : (cfg->rhs_id == ODEF_RHS_PLEIADES || cfg->rhs_id == ODEF_RHS_LORENZ96);
     if (team)
       return fail(nullptr, "odef_create: MV diffusion models run on the lane kernels only (state dimension d(q+1) <= 20, d <= 10); "
+                           "rhs %d with d = %d, d(q+1) = %d runs on the workgroup-per-trajectory kernels", cfg->rhs_id, cfg->d,
+                  cfg->d * (cfg->order + 1));
+  }
+  if (cfg->alg == ODEF_IEKS) {
+    if (!cfg->smooth) return fail(nullptr, "odef_create: IEKS always smooths (smooth = 1)");  // src/ieks.jl:39
+    // the IEKS step is built on the lane / row-team kernels only
+    const bool team = cfg->rhs_id >= kJitFirstId ? jit_team_path(cfg->d, cfg->order)
+                                                 : (cfg->rhs_id == ODEF_RHS_PLEIADES || cfg->rhs_id == ODEF_RHS_LORENZ96);
+    if (team)
+      return fail(nullptr, "odef_create: IEKS runs on the lane kernels only (state dimension d(q+1) <= 20, d <= 10); "
                            "rhs %d with d = %d, d(q+1) = %d runs on the workgroup-per-trajectory kernels", cfg->rhs_id, cfg->d,
                   cfg->d * (cfg->order + 1));
   }
@@ -387,7 +413,7 @@ int odef_create(odef_ctx** out, const odef_config* cfg) {
   c->field = field_launch(cfg->rhs_id);
   if (!c->field) {
     std::string jerr;
-    c->field = jit_field(cfg->rhs_id, c->q, cfg->alg == ODEF_EK1, is_mv(cfg->diffusion), team_abi_stamp(), jerr);
+    c->field = jit_field(cfg->rhs_id, c->q, is_ek1(cfg->alg), is_mv(cfg->diffusion), cfg->alg == ODEF_IEKS, team_abi_stamp(), jerr);
     if (!c->field) {
       g_create_error = "odef_create: " + jerr;  // the whole compiler log
       delete c;
@@ -463,6 +489,7 @@ int odef_set_problem(odef_ctx* c, const double* u0, const double* p, double t0) 
   HIPCHK(c, hipFree(tmp));
   c->t0 = t0;
   c->have_problem = true;
+  clear_lin(c);
   return 0;
 }
 
@@ -476,6 +503,7 @@ int odef_set_problem_device(odef_ctx* c, const double* d_u0, const double* d_p, 
     HIPCHK(c, hipMemcpyAsync(c->d_p, d_p, sizeof(double) * c->np * (c->cfg.params_shared ? 1 : N), hipMemcpyDeviceToDevice, c->stream));
   c->t0 = t0;
   c->have_problem = true;
+  clear_lin(c);
   return 0;
 }
 
@@ -496,6 +524,7 @@ int odef_set_problem_perturbed(odef_ctx* c, const double* base_u0, const double*
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->t0 = t0;
   c->have_problem = true;
+  clear_lin(c);
   return 0;
 }
 
@@ -584,6 +613,23 @@ int odef_solve_fixed(odef_ctx* c, const double* tgrid, int64_t n_t) {
   if (tgrid[0] != c->t0) return fail(c, "odef_solve_fixed: tgrid[0] = %g differs from t0 = %g", tgrid[0], c->t0);
   for (int64_t n = 0; n + 1 < n_t; ++n)
     if (!(tgrid[n + 1] > tgrid[n])) return fail(c, "odef_solve_fixed: tgrid must be strictly increasing (index %lld)", (long long)n);
+  // IEKS: the linearisation points of this iterate (alg.linearize_at = sol, src/ieks.jl:56-61), row s + 1 for step s -> s + 1
+  const double* lin = nullptr;
+  if (c->cfg.alg == ODEF_IEKS && lin_active(c)) {
+    Buf& b = c->f[ODEF_F_LINEARIZE_AT];
+    const size_t need = field_count(c, ODEF_F_LINEARIZE_AT, (long)n_t) * sizeof(double);
+    if (b.bound) {
+      if (b.bytes < need)
+        return fail(c, "odef_solve_fixed: the bound ODEF_F_LINEARIZE_AT buffer holds %zu bytes, the grid needs n_t * d * N * 8 = %zu",
+                    b.bytes, need);
+      b.valid = need;
+    } else if (c->lin_grid.size() != (size_t)n_t || std::memcmp(c->lin_grid.data(), tgrid, sizeof(double) * (size_t)n_t) != 0) {
+      return fail(c, "odef_solve_fixed: ODEF_F_LINEARIZE_AT holds the smoothed solution on another grid (%zu points, this one has %lld); "
+                     "evaluate that solution on the new grid (odef_dense_output) and bind the result (odef_bind_device)",
+                  c->lin_grid.size(), (long long)n_t);
+    }
+    lin = (const double*)b.ptr;
+  }
   if (set_device(c)) return -1;
   const long nsteps = (long)n_t - 1;
   c->adaptive = false;
@@ -647,6 +693,7 @@ int odef_solve_fixed(odef_ctx* c, const double* tgrid, int64_t n_t) {
   P.tab_idx = c->d_tab_idx;
   P.nsteps = nsteps;
   P.t0 = c->t0;
+  P.lin = lin;
   size_t have = 0;
   if (team_path(c)) {
     if (P.everystep) {  // the matrix-core kernel writes its records through the trajectory-major stage when all of them fit
@@ -659,8 +706,8 @@ int odef_solve_fixed(odef_ctx* c, const double* tgrid, int64_t n_t) {
     return fail(c, "odef_solve_fixed: n_traj * D(D+1)/2 * 8 bytes must stay below 2 GiB per save slot; shard the ensemble");
   }
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  const int rc = c->field->filter(c->q, c->cfg.alg == ODEF_EK1, P, c->stream, 0, have ? c->d_stage : nullptr, have, &c->stage_filter_recs);
-  if (rc) return fail(c, "odef_solve_fixed: no kernel for rhs %d order %d", c->cfg.rhs_id, c->q);
+  const int rc = c->field->filter(c->q, is_ek1(c->cfg.alg), P, c->stream, 0, have ? c->d_stage : nullptr, have, &c->stage_filter_recs);
+  if (rc) return fail(c, "odef_solve_fixed: no %skernel for rhs %d order %d", lin ? "IEKS " : "", c->cfg.rhs_id, c->q);
   std::snprintf(c->kname[0], sizeof c->kname[0], "%s", last_kernel());
   return finish_filter(c, 1);
 }
@@ -673,6 +720,9 @@ int odef_solve_adaptive(odef_ctx* c, double t1, double abstol, double reltol, do
   if (!(dt0 > 0.0)) return fail(c, "odef_solve_adaptive: dt0 must be positive");
   if (max_steps < 1) return fail(c, "odef_solve_adaptive: max_steps must be >= 1");
   if (c->cfg.save_mode != ODEF_SAVE_EVERYSTEP) return fail(c, "odef_solve_adaptive: needs ODEF_SAVE_EVERYSTEP");
+  if (c->cfg.alg == ODEF_IEKS && lin_active(c))
+    return fail(c, "odef_solve_adaptive: IEKS relinearisation runs on fixed grids (ODEF_F_LINEARIZE_AT is set; "
+                   "odef_bind_device(ctx, ODEF_F_LINEARIZE_AT, NULL, 0) empties it, the step is then EK1)");
   if ((size_t)c->TRI * (size_t)c->cfg.n_traj * sizeof(double) >= (1ull << 31))
     return fail(c, "odef_solve_adaptive: n_traj * D(D+1)/2 * 8 bytes must stay below 2 GiB per save slot; shard the ensemble");
   if (set_device(c)) return -1;
@@ -695,7 +745,7 @@ int odef_solve_adaptive(odef_ctx* c, double t1, double abstol, double reltol, do
   }
   HIPCHK(c, hipMemsetAsync(c->f[ODEF_F_T].ptr, 0, c->f[ODEF_F_T].valid, c->stream));
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
-  const int rc = c->field->filter(c->q, c->cfg.alg == ODEF_EK1, P, c->stream, 1, nullptr, 0, &c->stage_filter_recs);
+  const int rc = c->field->filter(c->q, is_ek1(c->cfg.alg), P, c->stream, 1, nullptr, 0, &c->stage_filter_recs);
   if (rc) return fail(c, "odef_solve_adaptive: no kernel for rhs %d order %d", c->cfg.rhs_id, c->q);
   std::snprintf(c->kname[0], sizeof c->kname[0], "%s", last_kernel());
   return finish_filter(c, 1);
@@ -756,6 +806,18 @@ int odef_smooth(odef_ctx* c) {
   std::snprintf(c->kname[1], sizeof c->kname[1], "%s", last_kernel());
   HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
   HIPCHK(c, hipGetLastError());
+  if (c->cfg.alg == ODEF_IEKS && !c->adaptive) {
+    // alg.linearize_at = sol (src/ieks.jl:58): the u rows of every smoothed mean into an owned ODEF_F_LINEARIZE_AT, one strided
+    // copy; the next odef_solve_fixed on this grid linearises there.  Caller memory is never written: a bound buffer is let go.
+    Buf& b = c->f[ODEF_F_LINEARIZE_AT];
+    if (b.bound) b = Buf{};
+    if (ensure(c, ODEF_F_LINEARIZE_AT, field_count(c, ODEF_F_LINEARIZE_AT, c->n_save) * sizeof(double))) return -1;
+    const size_t N = (size_t)c->cfg.n_traj, row = (size_t)c->d * N * sizeof(double);
+    HIPCHK(c, hipMemcpy2DAsync(b.ptr, row, c->f[ODEF_F_SMOOTH_MEAN].ptr, (size_t)c->D * N * sizeof(double), row, (size_t)c->n_save,
+                               hipMemcpyDeviceToDevice, c->stream));
+    c->lin_set = true;
+    c->lin_grid = c->tgrid;
+  }
   c->nl[1] = 1;
   c->smoothed_done = true;
   c->pending = 2;
@@ -912,10 +974,16 @@ int odef_get_device(odef_ctx* c, int field, void** dev_ptr, size_t* bytes) {
 int odef_bind_device(odef_ctx* c, int field, void* dev_ptr, size_t bytes) {
   if (!c) return -1;
   if (field < 0 || field >= ODEF_F_COUNT_ || field == ODEF_F_U0) return fail(c, "odef_bind_device: field %d cannot be bound", field);
+  if (field == ODEF_F_LINEARIZE_AT && dev_ptr && c->cfg.alg != ODEF_IEKS)
+    return fail(c, "odef_bind_device: ODEF_F_LINEARIZE_AT belongs to an IEKS context (alg = ODEF_IEKS)");
   if (set_device(c)) return -1;
   Buf& b = c->f[field];
   if (b.owned && b.ptr) HIPCHK(c, hipFree(b.ptr));
   b = Buf{};
+  if (field == ODEF_F_LINEARIZE_AT) {  // bound (caller memory, read only) or, with NULL, empty
+    c->lin_set = false;
+    c->lin_grid.clear();
+  }
   if (dev_ptr) {
     b.ptr = dev_ptr;
     b.bytes = bytes;

@@ -63,6 +63,17 @@ __global__ __launch_bounds__(kWave) void ek_filter_adaptive_mv_kernel(const Filt
   const long i0 = (long)blockIdx.x * kWave;
   if (i0 + threadIdx.x < P.N) filter_adaptive_lane<RHS, q, false, true>(P, i0, threadIdx.x);
 }
+// The IEKS step (P.lin set): EK1 with the Jacobian at the previous iterate's smoothed u, fixed grid, every step saved.  A
+// kernel of its own, so that the EK1 kernels above stay what they are.
+template <class RHS, int q, bool LAG>
+__global__ __launch_bounds__(kWave) void ek_filter_fixed_ieks_kernel(const FilterParams P) {
+  const long i0 = (long)blockIdx.x * kWave;
+  if (P.stagger > 0) {
+    const int n = (int)(blockIdx.x % 16u) * P.stagger;
+    for (int k = 0; k < n; ++k) __builtin_amdgcn_s_sleep(1);
+  }
+  if (i0 + threadIdx.x < P.N) filter_fixed_lane<RHS, q, true, true, LAG, false, true>(P, i0, threadIdx.x);
+}
 // Smoother: row-per-lane teams (smooth_rows.h), 16 lanes per trajectory for D <= 16 (4 trajectories per
 // wavefront), 32 lanes for D <= 32; per-team matrices in LDS.
 template <int D>
@@ -812,7 +823,9 @@ struct LaunchTeamSmooth {
 
 // WITH_MV: the MV-model kernels (EK0) are instantiated beside the scalar ones.  An MV context (P.fixed_diffusion 3 / 4) takes
 // the lane kernels at every ensemble size: the row-team filters (rows_filter.h) carry the scalar models only.
-template <bool WITH_MV = true>
+// WITH_IEKS: the IEKS kernels (EK1, fixed grid, every step saved) are instantiated beside the EK1 ones; P.lin picks them, at the
+// ensemble-size thresholds of the EK1 kernels.
+template <bool WITH_MV = true, bool WITH_IEKS = true>
 struct LaunchFilterT {
   const FilterParams& P;
   int adaptive;
@@ -821,6 +834,28 @@ struct LaunchFilterT {
   template <class RHS, int q, bool EK1>
   void operator()() {
     const unsigned grid = (unsigned)((P.N + kWave - 1) / kWave);
+    if (P.lin) {
+      if constexpr (WITH_IEKS && EK1) {
+        if (adaptive || !P.everystep || P.fixed_diffusion >= 3) {
+          rc = -2;
+          return;
+        }
+        if constexpr (RHS::d * (q + 1) <= kRowsMaxD) {
+          if (P.N < filter_rows_max_n()) {
+            note_kernel("odef::ek_filter_rows_ieks_kernel<odef::%s, %d>", RHS::name, q);
+            hipLaunchKernelGGL((ek_filter_rows_ieks_kernel<RHS, q>), dim3(rows_grid(P.N)), dim3(kRowsBlock), 0, s, P);
+            return;
+          }
+        }
+        const bool lag = P.N < filter_lag_max_n();
+        note_kernel("odef::ek_filter_fixed_ieks_kernel<odef::%s, %d, %s>", RHS::name, q, tf(lag));
+        if (lag) hipLaunchKernelGGL((ek_filter_fixed_ieks_kernel<RHS, q, true>), dim3(grid), dim3(kWave), 0, s, P);
+        else hipLaunchKernelGGL((ek_filter_fixed_ieks_kernel<RHS, q, false>), dim3(grid), dim3(kWave), 0, s, P);
+      } else {
+        rc = -2;
+      }
+      return;
+    }
     if (P.fixed_diffusion >= 3) {
       if constexpr (WITH_MV && !EK1) {
         if (adaptive) {
@@ -920,10 +955,11 @@ struct LaunchSmoothT {
 using LaunchSmooth = LaunchSmoothT<true>;
 
 // The launchers above with the signatures of a FieldLaunch table (launch.h); ONLYQ / ONLYEK1 as for dispatch_order.
-// WITH_MV: with the kernels of the MV diffusion models (a run-time compiled field builds them only for an MV context, jit.hip)
-template <class RHS, int ONLYQ = 0, bool ONLYEK1 = false, bool WITH_MV = true>
+// WITH_MV: with the kernels of the MV diffusion models (a run-time compiled field builds them only for an MV context, jit.hip);
+// WITH_IEKS: with the IEKS kernels (EK1 only; a run-time compiled field builds them only for an IEKS context)
+template <class RHS, int ONLYQ = 0, bool ONLYEK1 = false, bool WITH_MV = true, bool WITH_IEKS = true>
 int lane_filter(int q, int ek1, const FilterParams& P, hipStream_t s, int adaptive, double*, size_t, long*) {
-  LaunchFilterT<WITH_MV> f{P, adaptive, s};
+  LaunchFilterT<WITH_MV, WITH_IEKS> f{P, adaptive, s};
   const int rc = dispatch_order<RHS, ONLYQ, ONLYEK1>(q, ek1, f);
   return rc ? rc : f.rc;
 }

@@ -47,6 +47,9 @@ struct FilterParams {
   // trajectory-major into this stage (record_stage.h) and moved to `cov` by the host afterwards; null: written in place
   double* cov_stage;  // [n_save][N][stage_ld]
   long stage_ld;
+  // IEKS (ODEF_IEKS, fixed grid, every step saved): the linearisation points [n_t][d][N] -- the u part of the previous
+  // iterate's smoothed mean, step s -> s + 1 reads row s + 1 (src/perform_step.jl:111-125); null: the step is EK1
+  const double* lin;
 };
 
 // Row store: `base` is a wave-uniform pointer to element [field row 0][first trajectory of the
@@ -207,10 +210,12 @@ __device__ inline bool all_finite(const double (&m)[D]) {
 // its own branch, which cost 10 % in instructions and scheduling).
 // LAG (with EVERY): the record of step n is stored while step n + 1 runs (LaggedSink) -- for small ensembles.
 // MV: the diagonal diffusion models (EKStep), d diffusions per record.
-template <class RHS, int q, bool IS_EK1, bool EVERY, bool LAG = false, bool MV = false>
+// IEKS: the Jacobian of every step at P.lin (EKStep), EK1 and every step saved only.
+template <class RHS, int q, bool IS_EK1, bool EVERY, bool LAG = false, bool MV = false, bool IEKS = false>
 __device__ inline void filter_fixed_lane(const FilterParams& P, long i0, unsigned lane) {
+  static_assert(!IEKS || (IS_EK1 && EVERY && !MV), "IEKS: EK1, every step saved, scalar diffusion models");
   const long i = i0 + lane;
-  using S = EKStep<RHS, q, IS_EK1, MV>;
+  using S = EKStep<RHS, q, IS_EK1, MV, IEKS>;
   constexpr int d = S::d, D = S::D, TRI = S::TRI, np = RHS::np;
   double pl[np > 0 ? np : 1];
 #pragma unroll
@@ -236,9 +241,13 @@ __device__ inline void filter_fixed_lane(const FilterParams& P, long i0, unsigne
   for (long n = 0; n < P.nsteps; ++n) {
     const GlobalTab tab{P.ptab + (size_t)uniform_load(P.tab_idx + n) * kTabStride};  // wave-uniform, scalar loads
     double m2[D], C2[TRI], es[d];
-    std::conditional_t<MV, StepAuxMV<d>, StepAux> aux;
+    std::conditional_t<MV, StepAuxMV<d>, std::conditional_t<IEKS, StepAuxLin<d>, StepAux>> aux;
     aux.chol_fix = 0;
     const size_t Nn = (size_t)P.N;
+    if constexpr (IEKS) {  // this step's linearisation point, loaded first so that its latency hides behind the predict
+#pragma unroll
+      for (int a = 0; a < d; ++a) aux.u_lin[a] = P.lin[((size_t)(n + 1) * d + a) * Nn + i];
+    }
     if constexpr (EVERY && LAG) {  // record n = the inputs of this step
       LaggedSink<D, TRI, Diff> sink{m, C, gdiff,
                                     RowStore(P.mean + ((size_t)n * D * Nn + i0), Nn, D, lane),

@@ -419,11 +419,21 @@ struct StepAuxMV : StepAux {
   SigV<d> sig_local, sig_global;
 };
 
+// ... and of an IEKS step: the point the Jacobian is evaluated at (set by the caller before run)
+template <int d>
+struct StepAuxLin : StepAux {
+  double u_lin[d];
+};
+
 // MV: the diagonal diffusion models (EK0 only, src/diffusions.jl:96, :125); `fixed_diffusion` is then the C ABI's
 // odef_diffusion value 3 (:dynamicMV) or 4 (:fixedMV), `prev_global` a SigV<d> and `aux` a StepAuxMV<d>.
-template <class RHS, int q, bool IS_EK1, bool MV = false>
+// IEKS: the iterated extended Kalman smoother's step (src/perform_step.jl:111-125): `aux` is a StepAuxLin<d> whose `u_lin` holds
+// the linearisation point (the previous iterate's smoothed u at the new time), the Jacobian is evaluated there; f stays at the
+// prediction.
+template <class RHS, int q, bool IS_EK1, bool MV = false, bool IEKS = false>
 struct EKStep {
   static_assert(!(MV && IS_EK1), "MV diffusion models require EK0");
+  static_assert(!IEKS || IS_EK1, "IEKS is an EK1 step");
   static constexpr int d = RHS::d;
   static constexpr int NB = q + 1;
   static constexpr int D = d * NB;
@@ -488,7 +498,9 @@ struct EKStep {
     double H0[d][d];
     if constexpr (IS_EK1) {
       double Jm[d][d];
-      rhs_jacobian<RHS>(up, p, Jm);  // f.jac, else forward-mode AD (src/perform_step.jl:116-121)
+      // f.jac, else forward-mode AD (src/perform_step.jl:116-121); IEKS: at linearize_at(t).mu (:111-113)
+      if constexpr (IEKS) rhs_jacobian<RHS>(aux.u_lin, p, Jm);
+      else rhs_jacobian<RHS>(up, p, Jm);
 #pragma unroll
       for (int r = 0; r < d; ++r)
 #pragma unroll

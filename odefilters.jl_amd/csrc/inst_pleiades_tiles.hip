@@ -8,6 +8,7 @@
 #define ODEF_CAT(a, b) ODEF_CAT2(a, b)
 namespace odef {
 int ODEF_CAT(launch_filter_pleiades_tiles_q, ODEF_TILES_Q)(int ek1, const FilterParams& P, hipStream_t s, int adaptive) {
+  if (P.lin) return -6;  // no IEKS kernel on the workgroup-per-trajectory path
   LaunchTilesFilter f{P, s, adaptive};
   return dispatch_alg<RhsPleiades, ODEF_TILES_Q>(ek1, f);
 }

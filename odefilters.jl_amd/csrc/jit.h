@@ -16,7 +16,8 @@ bool jit_lookup(int rhs_id, int* d, int* np);
 // into a host + device shared object around the field (seconds; minutes on the workgroup-per-trajectory kernels).
 // abi_stamp: team_abi_stamp() of the library
 struct FieldLaunch;
-// mv: the MV diffusion models' kernels are built (only) for an MV context -- a module of its own, the key includes it
-const FieldLaunch* jit_field(int rhs_id, int q, int ek1, int mv, unsigned long abi_stamp, std::string& err);
+// mv: the MV diffusion models' kernels are built (only) for an MV context -- a module of its own, the key includes it;
+// ieks: the same for the IEKS kernels and an IEKS context
+const FieldLaunch* jit_field(int rhs_id, int q, int ek1, int mv, int ieks, unsigned long abi_stamp, std::string& err);
 
 }  // namespace odef

@@ -40,7 +40,7 @@ struct JitRhs {
 
 std::mutex g_mu;
 std::vector<JitRhs> g_rhs;                                                      // id = kJitFirstId + index
-std::map<std::tuple<int, int, int, int>, const FieldLaunch*> g_fields;           // (id, q, ek1, mv): shared objects, never unloaded
+std::map<std::tuple<int, int, int, int, int>, const FieldLaunch*> g_fields;      // (id, q, ek1, mv, ieks): shared objects, never unloaded
 
 // path of this library (the run-time compiled shared objects link against it: note_kernel)
 std::string this_library() {
@@ -72,8 +72,8 @@ std::string default_include_dir() {
 // the lane / row-team ones of ek_kernels.h up to state dimension 20, the workgroup-per-trajectory ones of team_launch_impl.h
 // above (exactly what inst_lorenz63.hip / inst_lorenz96.hip are for a compiled-in field) -- exporting their table.
 // mv: with the kernels of the MV diffusion models (lane path, EK0; an MV context only, so that a scalar-model module is not
-// built any slower)
-std::string module_source(const JitRhs& r, int q, int ek1, int mv) {
+// built any slower); ieks: with the IEKS kernels (lane path, EK1; an IEKS context only, likewise)
+std::string module_source(const JitRhs& r, int q, int ek1, int mv, int ieks) {
   const int D = r.d * (q + 1);
   const bool team = jit_team_path(r.d, q);
   const std::string Q = std::to_string(q), EK = ek1 ? "true" : "false", DD = std::to_string(r.d), MV = mv ? "true" : "false",
@@ -94,7 +94,7 @@ std::string module_source(const JitRhs& r, int q, int ek1, int mv) {
     s += "team_filter<RhsJit, " + Q + ", " + EK + ">, team_smooth_inplace<" + TT + ">, team_smooth_staged<" + TT + ">, team_dense<" + TT +
          ">, team_sample<" + TT + ">, team_smooth_ws<" + TT + ">";
   else
-    s += "lane_filter<RhsJit, " + Q + ", " + EK + ", " + MV + ">, lane_smooth<" + T + ">, nullptr, lane_dense<" + T + ">, lane_sample<" + T + ">, nullptr";
+    s += "lane_filter<RhsJit, " + Q + ", " + EK + ", " + MV + ", " + (ieks ? "true" : "false") + ">, lane_smooth<" + T + ">, nullptr, lane_dense<" + T + ">, lane_sample<" + T + ">, nullptr";
   s += "};\n  return &t;\n}\n";
   return s;
 }
@@ -359,7 +359,7 @@ int jit_register(const char* name, const char* source, int d, int np, const char
   JitRhs r{name, source, include_dir ? include_dir : "", d, np};
   // compile the order-1 EK1 module (d <= 10; a probe kernel above) once now so that errors in the user's text surface here,
   // with the compiler log
-  if (!compile(d <= 10 ? module_source(r, 1, 1, 0) : probe_translation_unit(r), r.include_dir, err)) return -1;
+  if (!compile(d <= 10 ? module_source(r, 1, 1, 0, 0) : probe_translation_unit(r), r.include_dir, err)) return -1;
   std::lock_guard<std::mutex> lk(g_mu);
   g_rhs.push_back(std::move(r));
   return kJitFirstId + (int)g_rhs.size() - 1;
@@ -374,11 +374,11 @@ bool jit_lookup(int rhs_id, int* d, int* np) {
   return true;
 }
 
-const FieldLaunch* jit_field(int rhs_id, int q, int ek1, int mv, unsigned long abi_stamp, std::string& err) {
+const FieldLaunch* jit_field(int rhs_id, int q, int ek1, int mv, int ieks, unsigned long abi_stamp, std::string& err) {
   // The hipcc child process takes seconds to minutes: it runs OUTSIDE the registry lock, so that odef_create for other
   // vector fields (jit_lookup, cached modules) is not blocked meanwhile.  Two threads asking for the same uncached
   // module may both compile; the first to publish wins.
-  const auto key = std::make_tuple(rhs_id, q, ek1, mv ? 1 : 0);
+  const auto key = std::make_tuple(rhs_id, q, ek1, mv ? 1 : 0, ieks ? 1 : 0);
   JitRhs r;
   {
     std::lock_guard<std::mutex> lk(g_mu);
@@ -392,7 +392,7 @@ const FieldLaunch* jit_field(int rhs_id, int q, int ek1, int mv, unsigned long a
     r = g_rhs[k];  // copy: the vector may grow while we compile
   }
   void* handle = nullptr;
-  if (!compile(module_source(r, q, ek1, mv), r.include_dir, err, &handle)) return nullptr;
+  if (!compile(module_source(r, q, ek1, mv, ieks), r.include_dir, err, &handle)) return nullptr;
   using Entry = const FieldLaunch* (*)();
   using Stamp = unsigned long (*)();
   const Entry entry = (Entry)dlsym(handle, "odef_jit_field");

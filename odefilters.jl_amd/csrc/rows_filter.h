@@ -107,8 +107,10 @@ struct RowsScale {
   }
 };
 
-template <class RHS, int q, bool IS_EK1>
+// IEKS: the Jacobian at the linearisation point `u_lin` of `run` (team-uniform, every lane its copy), as EKStep.
+template <class RHS, int q, bool IS_EK1, bool IEKS = false>
 struct RowsStep {
+  static_assert(!IEKS || IS_EK1, "IEKS is an EK1 step");
   static constexpr int d = RHS::d, NB = q + 1, D = d * NB, LD = tv::lds_ld(D);
   static constexpr int kLdsDoubles = tv::lds_rows(d, NB) * LD;  // the team's exchange rows
   // adaptive kernel: + the lanes' rows of Q and the state before the attempt (restored when it is rejected), both kept
@@ -123,7 +125,8 @@ struct RowsStep {
   __device__ static inline void run(const PriorConsts& pc, const RowsConsts<d, NB>& lc, const RowsScale<d, NB>& sc,
                                     const double* __restrict__ pl, int fixed_diffusion, bool want_loglik, int success_iter,
                                     double prev_global, const tv::Lds& lds, TV& m, TV (&xr)[D], double (&err_scale)[d],
-                                    StepAux& aux, int qm_lds_off = -1) {  // qm_lds_off >= 0: the lanes' rows of Q are in LDS there
+                                    StepAux& aux, int qm_lds_off = -1,  // qm_lds_off >= 0: the lanes' rows of Q are in LDS there
+                                    const double (*u_lin)[d] = nullptr) {
     const double pi0 = sc.pijv[0], pi1 = sc.pijv[1];
     // x~ = P x (src/perform_step.jl:36-38)
     const TV mt = sc.pj * m;
@@ -148,7 +151,8 @@ struct RowsStep {
     double H0[d][d];  // H = (E1 - J E0) P^-1 -> blocks H0 = -J pi0, H1 = pi1 I;  EK0: H0 = 0
     if constexpr (IS_EK1) {
       double Jm[d][d];
-      rhs_jacobian<RHS>(up, pl, Jm);
+      if constexpr (IEKS) rhs_jacobian<RHS>(*u_lin, pl, Jm);  // src/perform_step.jl:111-113
+      else rhs_jacobian<RHS>(up, pl, Jm);
 #pragma unroll
       for (int r = 0; r < d; ++r)
 #pragma unroll
@@ -399,9 +403,11 @@ __device__ inline void rows_initial_state(const FilterParams& P, long i, double 
 
 // Whole fixed-grid time loop of the team's trajectory (OrdinaryDiffEq's solve! loop on the device).
 // Workgroup-collective when EVERY (rows_store.h): all 16 teams of the workgroup run the same number of steps.
-template <class RHS, int q, bool IS_EK1, bool EVERY>
+// IEKS: every lane of the team loads the step's linearisation point (row n + 1 of P.lin) itself, as it holds `up`.
+template <class RHS, int q, bool IS_EK1, bool EVERY, bool IEKS = false>
 __device__ inline void rows_filter_fixed(const FilterParams& P, const RowsTeam& tm) {
-  using S = RowsStep<RHS, q, IS_EK1>;
+  static_assert(!IEKS || (IS_EK1 && EVERY), "IEKS: EK1, every step saved");
+  using S = RowsStep<RHS, q, IS_EK1, IEKS>;
   constexpr int d = S::d, NB = S::NB, D = S::D, np = RHS::np;
   const long i = tm.i;
   const tv::Lds lds{tm.lds_team};
@@ -433,7 +439,12 @@ __device__ inline void rows_filter_fixed(const FilterParams& P, const RowsTeam& 
     double es[d];
     StepAux aux;
     aux.chol_fix = 0;
-    S::run(P.pc, lc, sc, pl, P.fixed_diffusion, P.want_loglik != 0, (int)n, gdiff, lds, m, xr, es, aux);
+    double ul[d];
+    if constexpr (IEKS) {
+#pragma unroll
+      for (int a = 0; a < d; ++a) ul[a] = P.lin[((size_t)(n + 1) * d + a) * (size_t)P.N + i];
+    }
+    S::run(P.pc, lc, sc, pl, P.fixed_diffusion, P.want_loglik != 0, (int)n, gdiff, lds, m, xr, es, aux, -1, IEKS ? &ul : nullptr);
     loglik += aux.loglik;
     if (P.want_loglik) lda.mul(aux.det);
     gdiff = aux.sigma2_global;

@@ -27,6 +27,7 @@ int team_filter_staged(int q, int ek1, const FilterParams& P, hipStream_t s, int
                        bool valu_kernel_selected, ByOrder&& by_order, long* staged_recs) {
   const long D = (long)d * (q + 1), TRI = D * (D + 1) / 2, ld = stage_record_ld(TRI), n_rec = P.nsteps + 1;
   if (staged_recs) *staged_recs = 0;
+  if (P.lin) return -6;  // no IEKS kernel on this path (odef_create refuses it): never run EK1 in its place
   if (adaptive || !P.everystep || valu_kernel_selected || !stage || (size_t)n_rec * (size_t)P.N * (size_t)ld > stage_doubles)
     return by_order(q, ek1, P, s, adaptive);
   FilterParams PS = P;

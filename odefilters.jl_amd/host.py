@@ -23,7 +23,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ODEFILTER_HIP_LIB") or os.path.join(_HERE, "lib", "libodefilter_hip.so")
 
 # ---- enums (include/odefilter.h) ---------------------------------------------------------
-EK0_ID, EK1_ID = 0, 1
+EK0_ID, EK1_ID, IEKS_ID = 0, 1, 2
 DIFFUSION = {"dynamic": 0, "fixed": 1, "fixedMAP": 2, "dynamicMV": 3, "fixedMV": 4}
 # the diagonal ("multivariate") models: one diffusion per state component, EK0 on the lane kernels only (include/odefilter.h)
 MV_DIFFUSIONS = ("dynamicMV", "fixedMV")
@@ -33,7 +33,8 @@ RHS_DIMS = {"fhn": (2, 3), "lorenz63": (3, 3), "lotka_volterra": (2, 4), "vander
 SAVE_FINAL, SAVE_EVERYSTEP = 0, 1
 RETCODES = {0: "Success", 1: "MaxIters", 2: "DtLessThanMin", 3: "Unstable", 4: "Unstable"}
 (F_MEAN, F_COV_TRIL, F_DIFFUSION, F_T, F_LOGLIK, F_NACCEPT, F_NREJECT, F_NF, F_NJAC, F_NSAVED, F_RETCODE,
- F_SMOOTH_MEAN, F_SMOOTH_COV_TRIL, F_U0, F_DENSE_MEAN, F_DENSE_COV_TRIL, F_SAMPLES) = range(17)
+ F_SMOOTH_MEAN, F_SMOOTH_COV_TRIL, F_U0, F_DENSE_MEAN, F_DENSE_COV_TRIL, F_SAMPLES, F_LINEARIZE_AT) = range(18)
+ODEF_F_LINEARIZE_AT = F_LINEARIZE_AT  # IEKS linearisation points [n_save][d][N] (include/odefilter.h)
 _INT_FIELDS = {F_NACCEPT, F_NREJECT, F_NF, F_NJAC, F_NSAVED, F_RETCODE}
 MAX_ORDER = 5
 
@@ -200,6 +201,22 @@ class DeviceGroup:
     def smooth(self):
         self._chk(self.lib.odef_group_smooth(self._h))
 
+    def solve_ieks(self, tgrid, iterations=10):
+        """`solve_ieks` on every shard (an IEKS group, alg=IEKS_ID): the field of linearisation points starts empty (the first
+        iteration is EK1), then each iteration is one fixed-grid solve plus the smoother, whose result the next solve linearises
+        at -- all on the devices."""
+        if iterations < 1:
+            raise OdefError("solve_ieks: iterations must be >= 1")
+        for g in range(self.G):
+            self._chk_ctx(g, self.lib.odef_bind_device(self.lib.odef_group_ctx(self._h, g), F_LINEARIZE_AT, None, 0))
+        for _ in range(int(iterations)):
+            self.solve_fixed(tgrid)
+            self.smooth()
+
+    def _chk_ctx(self, g, rc):
+        if rc != 0:
+            raise OdefError(self.lib.odef_last_error(self.lib.odef_group_ctx(self._h, g)).decode())
+
     def allgather(self, smoothed=False, from_device=0) -> np.ndarray:
         """Final posterior means of the WHOLE ensemble, [D, N], as device `from_device` holds them after the all-gather."""
         self._chk(self.lib.odef_allgather(self._h, int(smoothed)))
@@ -228,6 +245,8 @@ class DeviceGroup:
                 out = out.reshape(-1, self.TRI, n)
             elif f == F_DIFFUSION:
                 out = out.reshape(-1, self.d, n) if self.mv else out.reshape(-1, n)
+            elif f == F_LINEARIZE_AT:
+                out = out.reshape(-1, self.d, n)
             parts.append(out)
         return np.concatenate(parts, axis=-1)
 
@@ -407,6 +426,8 @@ class Context:
             return out.reshape(ns, N) if out.size == ns * N and out.size != ns else out
         if f == F_U0:
             return out.reshape(self.d, N)
+        if f == F_LINEARIZE_AT:
+            return out.reshape(-1, self.d, N)
         return out
 
     def device_ptr(self, f: int):
@@ -522,6 +543,35 @@ class EK1:
     diffusionmodel: str = "dynamic"
     smooth: bool = True
     _id = EK1_ID
+
+
+class IEKS:
+    """`IEKS(; prior=:ibm, order=1, diffusionmodel=:dynamic, linearize_at=nothing)` (src/ieks.jl:2-41): the iterated extended
+    Kalman smoother of Tronarp et al.  `smooth` is always true.  `linearize_at`: a previous IEKS or EK1 `EnsembleSolution`
+    (smoothed, same prior, order and diffusion model, same ensemble size) whose smoothed u the Jacobians of a plain
+    `solve(prob, IEKS(linearize_at=sol), ...)` are evaluated at; `solve_ieks` ignores it and starts from EK1, as the
+    reference's loop does."""
+    _id = IEKS_ID
+    smooth = True
+
+    def __init__(self, prior: str = "ibm", order: int = 1, diffusionmodel: str = "dynamic", linearize_at=None):
+        if linearize_at is not None:  # src/ieks.jl:32-38
+            if not isinstance(linearize_at, EnsembleSolution):
+                raise AssertionError("linearize_at must be a solution (EnsembleSolution)")
+            la = linearize_at.alg
+            if la.prior != prior:
+                raise AssertionError(f"linearize_at was solved with prior {la.prior!r}, not {prior!r}")
+            if la.order != order:
+                raise AssertionError(f"linearize_at was solved with order {la.order}, not {order}")
+            if la.diffusionmodel != diffusionmodel:
+                raise AssertionError(f"linearize_at was solved with diffusionmodel {la.diffusionmodel!r}, not {diffusionmodel!r}")
+            if not la.smooth:
+                raise AssertionError("linearize_at must be a smoothed solution (smooth=true)")
+        self.prior, self.order, self.diffusionmodel, self.linearize_at = prior, order, diffusionmodel, linearize_at
+
+    def __repr__(self):
+        return (f"IEKS(prior={self.prior!r}, order={self.order}, diffusionmodel={self.diffusionmodel!r}, "
+                f"linearize_at={'None' if self.linearize_at is None else 'EnsembleSolution'})")
 
 
 @dataclass
@@ -841,6 +891,9 @@ def solve(prob, alg, ensemblealg: EnsembleHIP = EnsembleHIP(), *, trajectories: 
         raise OdefError(f"diffusionmodel {alg.diffusionmodel!r} is not on the device path; use one of {sorted(DIFFUSION)}")
     if alg.diffusionmodel in MV_DIFFUSIONS and alg._id != EK0_ID:
         raise OdefError("MV diffusion models require EK0")  # src/diffusions.jl:96, :125
+    lin_sol = getattr(alg, "linearize_at", None)
+    if lin_sol is not None and adaptive:
+        raise OdefError("IEKS relinearisation runs on fixed grids: pass adaptive=False and dt (or tstops)")
     if not adaptive and dt is None and tstops is None:
         # test/errors.jl:17-19
         raise OdefError("Fixed timestep methods require a choice of dt or choosing the tstops")
@@ -854,6 +907,8 @@ def solve(prob, alg, ensemblealg: EnsembleHIP = EnsembleHIP(), *, trajectories: 
             raise OdefError("trajectories is required")
         N = trajectories
     t0, t1 = float(base.tspan[0]), float(base.tspan[1])
+    if lin_sol is not None and lin_sol.ctx.N != N:
+        raise OdefError(f"IEKS: linearize_at holds {lin_sol.ctx.N} trajectories, this ensemble has {N}")
     shared = prob.ps is None
     ctx = Context(base.f, alg.order, alg._id, N, diffusion=alg.diffusionmodel, smooth=alg.smooth,
                   save_everystep=save_everystep, params_shared=shared, device=ensemblealg.device,
@@ -878,6 +933,8 @@ def solve(prob, alg, ensemblealg: EnsembleHIP = EnsembleHIP(), *, trajectories: 
         ctx.solve_adaptive(t1, abstol, reltol, dt if dt is not None else 1e-3 * (t1 - t0), None, ms)
     else:
         grid = np.asarray(tstops, float) if (tstops is not None and dt is None) else fixed_time_grid(t0, t1, dt, tstops)
+        if lin_sol is not None:
+            _bind_linearization(ctx, lin_sol, grid)
         ctx.solve_fixed(grid)
     sol = EnsembleSolution(ctx, alg, adaptive)
     sol.shard = shard
@@ -891,3 +948,44 @@ def solve(prob, alg, ensemblealg: EnsembleHIP = EnsembleHIP(), *, trajectories: 
         warnings.warn(f"{bad.size} of {N} trajectories did not finish with Success ({', '.join(kinds)}; first: trajectory "
                       f"{int(bad[0])}); see sol.retcode", RuntimeWarning, stacklevel=2)
     return sol
+
+
+def _bind_linearization(ctx: Context, lin_sol: EnsembleSolution, grid: np.ndarray) -> None:
+    """IEKS(linearize_at = lin_sol): bind the smoothed u of `lin_sol` on `grid` as ODEF_F_LINEARIZE_AT [n_t][d][N] -- its
+    smoothed records when it was solved on this grid (linearize_at(t) at a save time is that record), else its smoothed dense
+    output `lin_sol(grid)`.  The buffer is device memory owned by torch, kept alive by the context."""
+    import torch
+
+    same = not lin_sol.adaptive and lin_sol.t.shape == grid.shape and np.array_equal(lin_sol.t, grid)
+    u = lin_sol.x_smooth_mean() if same else lin_sol(grid, smoothed=True)[0]  # [N, n_t, D]
+    lin = np.ascontiguousarray(u[:, :, : ctx.d].transpose(1, 2, 0))
+    dev = int(ctx.cfg.device) if ctx.cfg.device >= 0 else torch.cuda.current_device()
+    buf = torch.from_numpy(lin).to(torch.device("cuda", dev))
+    torch.cuda.synchronize(dev)
+    ctx.bind_device(F_LINEARIZE_AT, buf.data_ptr(), buf.numel() * 8)
+    ctx._lin_buf = buf
+
+
+def solve_ieks(prob, alg: IEKS, ensemblealg: EnsembleHIP = EnsembleHIP(), *, iterations: int = 10, **kw) -> EnsembleSolution:
+    """`solve_ieks(prob, IEKS(...); iterations=10, kwargs...)` (src/ieks.jl:52-61): `iterations` complete solves (filter,
+    postamble, smoother) of the same problem on one fixed grid, each linearising at the previous one's smoothed u, with no
+    stopping criterion.  The first iteration is EK1 whatever `alg.linearize_at` holds, as in the reference's loop.  Every
+    iteration reuses one device context: the smoother leaves the next linearisation points on the device
+    (ODEF_F_LINEARIZE_AT), nothing goes through the host between iterations.  The result is the last iteration's solution
+    (its destats and log-likelihood are that solve's), with `sol.alg` = `alg`.  Fixed grids only (`adaptive=False` with `dt`
+    or `tstops`): relinearising an adaptive solve is out of scope."""
+    if not isinstance(alg, IEKS):
+        raise OdefError("solve_ieks needs an IEKS algorithm")
+    if kw.get("adaptive", True):
+        raise OdefError("IEKS relinearisation runs on fixed grids: solve_ieks needs adaptive=False and dt (or tstops)")
+    if int(iterations) < 1:
+        raise OdefError("solve_ieks: iterations must be >= 1")
+    first = IEKS(prior=alg.prior, order=alg.order, diffusionmodel=alg.diffusionmodel)  # sol = nothing (src/ieks.jl:56)
+    sol = solve(prob, first, ensemblealg, **kw)
+    ctx, grid = sol.ctx, np.asarray(sol.t, float)
+    for _ in range(int(iterations) - 1):  # alg.linearize_at = sol; sol = solve(prob, alg) -- on the device
+        ctx.solve_fixed(grid)
+        ctx.smooth()
+    out = EnsembleSolution(ctx, alg, False)
+    out.shard = sol.shard
+    return out
