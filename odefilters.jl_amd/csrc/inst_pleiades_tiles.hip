@@ -1,6 +1,6 @@
 // One order of the register-tiled Pleiades filter (filter_tiles.h): EK0/EK1 x fixed grid/adaptive.
 // Compiled five times with -DODEF_TILES_Q=1..5 (csrc/Makefile) so that the orders build in parallel.
-#include "ek_kernels.h"
+#include "team_kernels.h"
 #ifndef ODEF_TILES_Q
 #error "compile with -DODEF_TILES_Q=<order>"
 #endif

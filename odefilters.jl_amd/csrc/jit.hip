@@ -70,7 +70,7 @@ std::string default_include_dir() {
 
 // The module of one order and algorithm: the launchers of the compiled-in fields instantiated around the user's struct --
 // the lane / row-team ones of ek_kernels.h up to state dimension 20, the workgroup-per-trajectory ones of team_launch_impl.h
-// above (exactly what inst_lorenz63.hip / inst_lorenz96.hip are for a compiled-in field) -- exporting their table.
+// (kernels: team_kernels.h) above (exactly what inst_lorenz63.hip / inst_lorenz96.hip are for a compiled-in field) -- exporting their table.
 // mv: with the kernels of the MV diffusion models (lane path, EK0; an MV context only, so that a scalar-model module is not
 // built any slower); ieks: with the IEKS kernels (lane path, EK1; an IEKS context only, likewise)
 std::string module_source(const JitRhs& r, int q, int ek1, int mv, int ieks) {

@@ -32,8 +32,7 @@ __device__ inline RowsTeam rows_team(long N, double* lds, int team_doubles) {
   tm.stage = lds + kRowsWgTeams * team_doubles;
   return tm;
 }
-// (the kernel bodies are device functions so that the run-time compiled kernels of user vector fields -- extern "C" wrappers
-// generated by jit.hip -- are the very same code)
+// (each kernel is a one-line wrapper around an always-inline entry, so that its modes -- EVERY, IEKS -- share one body)
 template <class RHS, int q, bool EK1, bool EVERY, bool IEKS = false>
 __device__ __attribute__((always_inline)) inline void rows_filter_fixed_entry(const FilterParams& P) {
   using L = RowsLds<RHS::d, q + 1, EVERY ? RowsSink<RHS::d*(q + 1), true, false>::kStageDoubles : 0>;

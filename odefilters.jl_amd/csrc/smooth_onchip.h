@@ -1,6 +1,6 @@
 // The covariance products of one RTS step on chip (src/smoothing.jl:45-63 in the textbook form, see smooth_mfma.h):
 //   R = G M G' = Z' G',  Z = M G'        (M = P Sigma^s_+ P - B symmetric, G' = B^-1 A X)
-// for the workgroup that has just finished the two sweeps (ek_kernels.h, rts_smooth_sweeps_kernel): wavefront c holds tile
+// for the workgroup that has just finished the two sweeps (team_kernels.h, rts_smooth_sweeps_kernel): wavefront c holds tile
 // column c of G' in its accumulators (DPB tiles of 16 x 16, register v of a tile = rows 4 v + l / 16, column l % 16 -- which
 // IS the B operand of a K = 16 product).  Nothing of G' or Z goes through memory:
 //

@@ -2,7 +2,7 @@
 // record stage), written once for any vector field with an even d <= 32 and instantiated per field (inst_pleiades.hip: d = 28,
 // with the register-tiled VALU filter of round 1 as an alternate; inst_lorenz96.hip: d = 16, matrix cores only).
 #pragma once
-#include "ek_kernels.h"
+#include "team_kernels.h"
 
 namespace odef {
 
@@ -55,13 +55,11 @@ int team_filter(int q, int ek1, const FilterParams& P, hipStream_t s, int adapti
 // ensemble -- every trajectory joins in at the block that holds its own last record).  stage_doubles must hold at
 // least two records.  filter_recs_in_stage == n_rec: the filter has left all its records in `stage` (team_filter_staged; record r
 // at r N ld, stage_doubles counted from record 1) -- the pass then runs as one block on them, nothing is copied in.
-// Y' = A X formed by the on-chip kernel from the packed record (d a multiple of 4: register-local, ek_kernels.h) instead of
+// Y' = A X formed by the on-chip kernel from the packed record (d a multiple of 4: register-local, team_kernels.h) instead of
 // written by the predict kernel and read back; ODEF_SMOOTH_YFROMX=0: the hand-over through the workspace (A/B, and any other d)
 template <int d>
 inline bool smooth_y_from_record() {
-  if (d % 4 != 0) return false;
-  const char* e = getenv("ODEF_SMOOTH_YFROMX");
-  return !(e && e[0] == '0');
+  return d % 4 == 0 && !env_starts("ODEF_SMOOTH_YFROMX", '0');
 }
 template <int d, int ONLYQ = 0>
 int team_smooth_staged(int q, const SmoothParams& P0, long n_rec, double* ws, double* stage, size_t stage_doubles, hipStream_t s,

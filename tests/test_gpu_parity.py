@@ -141,7 +141,7 @@ def test_row_team_filter_equals_lane_filter(pkg, monkeypatch):
 
 @pytest.mark.parametrize("adaptive", [False, True])
 def test_both_small_state_smoothers_against_oracle(pkg, adaptive, monkeypatch):
-    """D <= 12 has three smoother kernels, chosen by ensemble size (csrc/ek_kernels.h LaunchSmooth): DPP row teams for small
+    """D <= 12 has three smoother kernels, chosen by ensemble size (csrc/ek_kernels.h LaunchSmoothT): DPP row teams for small
     ensembles, LDS row teams, one lane per trajectory for large ones.  The environment switches the launcher reads at every
     launch force each in turn."""
     vf = orc.vector_field("lorenz63")

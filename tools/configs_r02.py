@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""BASELINE.json configurations 2-5 as the library runs them by default (kernel selection of csrc/ek_kernels.h), one
-JSON line each: kernel times from the library's hipEvents (median of `--reps` launches after a warm-up), the
-algorithmic bytes / flops of SURVEY.md 8(d) and the roofline fraction they give.  `--only 2,5` restricts the list
+"""BASELINE.json configurations 2-5 as the library runs them by default (kernel selection of csrc/ek_kernels.h and
+csrc/team_kernels.h), one JSON line each: kernel times from the library's hipEvents (median of `--reps` launches after a
+warm-up), the algorithmic bytes / flops of SURVEY.md 8(d) and the roofline fraction they give.  `--only 2,5` restricts the list
 (used under rocprofv3, where one configuration per run keeps the traces apart)."""
 import argparse, json, os, sys
 import numpy as np

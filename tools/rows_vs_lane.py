@@ -2,7 +2,7 @@
 """Row-team filter (csrc/rows_filter.h, 16 lanes per trajectory) against the lane filter (one lane per trajectory):
 kernel time of the Lorenz-63 EK1(3) filter -- fixed step (1 024 steps, every step saved / final state only) and adaptive
 (t in [0, 2], abstol 1e-6, reltol 1e-3) -- per ensemble size.  One JSON line per size; the launcher's crossover
-(kFilterRowsMaxN, ek_kernels.h) is read off this table (profiles/r02_rows_vs_lane.jsonl)."""
+(kFilterRowsMaxN, rows_launch.h) is read off this table (profiles/r02_rows_vs_lane.jsonl)."""
 import json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,9 +1,9 @@
 // Where does a record of the D = 168 smoother's split pass spend its time?  Diagnostic build with wall-clock stamps at the
-// phase boundaries of workgroup 0 of the on-chip kernel (rts_smooth_sweeps_kernel, csrc/ek_kernels.h), run on a synthetic
+// phase boundaries of workgroup 0 of the on-chip kernel (rts_smooth_sweeps_kernel, csrc/team_kernels.h), run on a synthetic
 // set of staged filter records (random SPD covariances of Pleiades size) with N trajectories, and the time per launch of
 // both kernels of the pass (rts_smooth_predict_kernel, rts_smooth_sweeps_kernel).
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++20 -DODEF_SWEEPS_STAMPS -I odefilters.jl_amd/csrc tools/split_smooth_stamps.hip -o tools/_bin/split_smooth_stamps
-#include "ek_kernels.h"
+#include "team_kernels.h"
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>

@@ -2,7 +2,7 @@
 // (filter_tiles.h compiled with -DODEF_TILES_STAMPS).  Prints the share of each segment of the step.
 // Never quote this build's run time (the stamps serialise); read the shares.
 #define ODEF_TILES_STAMPS 1
-#include "../odefilters.jl_amd/csrc/ek_kernels.h"
+#include "../odefilters.jl_amd/csrc/team_kernels.h"
 #include <cstdio>
 #include <cstring>
 #include <cmath>
