@@ -34,6 +34,8 @@
  *   odef_smooth_step                predict!, update!, smooth (pure functions)   src/filtering.jl:17,79,136
  *   odef_ibm / odef_preconditioner  ibm(d,q), preconditioner(T,d,q)              src/priors.jl:7-59,
  *                                                                                src/preconditioning.jl:1-17
+ *   odef_summary_field ids          nothing in the reference: per-time mean and covariance of the ensemble's Gaussian mixture,
+ *                                   reduced on the device and read with odef_get (see odef_summary_field)
  *   odef_group_* / odef_allgather   nothing in the reference (it has no ensemble and no distributed code):
  *                                   the EnsembleProblem axis sharded over the GPUs of one node by ONE host process, the
  *                                   per-trajectory path above unchanged on every shard, one RCCL all-gather at the end
@@ -135,6 +137,39 @@ typedef enum {
   ODEF_F_LINEARIZE_AT = 17,    /* [n_save][d][N] IEKS linearisation points (see odef_alg) */
   ODEF_F_COUNT_
 } odef_field;
+
+/* Ensemble summary per time, reduced on the device (nothing in the reference: it has no ensemble).  For one time and the n
+ * trajectories that are INCLUDED there -- RETCODE == ODEF_RET_SUCCESS and the d solution entries of the mean at that time finite --
+ * with mu_i the solution part of the posterior mean (rows 0..d-1 of a record) and Sigma_i the d x d solution block of its covariance:
+ *   COUNT        n                                              int64  [n_t]
+ *   MEAN         m = (1/n) sum_i mu_i                           double [n_t][d]
+ *   COV_WITHIN   W = (1/n) sum_i Sigma_i                        double [n_t][d(d+1)/2] packed lower triangle, (k,l), k>=l at k(k+1)/2+l
+ *   COV_BETWEEN  B = (1/n) sum_i (mu_i - m)(mu_i - m)'          double [n_t][d(d+1)/2]
+ * m and W + B are the mean and covariance of the equal-weight mixture of the trajectories' Gaussian posteriors.  The divisor is n;
+ * with n = 0 the three moments are NaN.  Field id = ODEF_S_BASE + 8 * source + quantity, source 0: the filter records (n_t =
+ * odef_n_save), 1: the smoothed records, 2: the last odef_dense_output / odef_dense_sample result (n_t = n_q).  odef_field_bytes,
+ * odef_get and odef_get_device accept these ids (odef_bind_device does not).  The first request for a source after its records
+ * changed runs the reduction on the context's stream (two passes, the covariance of the means is centred before it is squared;
+ * deterministic, no floating-point atomics) and caches the four arrays; odef_solve_*, odef_smooth, odef_dense_output,
+ * odef_dense_sample and odef_set_problem* invalidate them.  Refused with a message: any source before a solve, source 1 before
+ * odef_smooth, source 2 before a dense output, sources 0 / 1 after an ADAPTIVE solve (the records of one save index lie at
+ * different times per trajectory: evaluate odef_dense_output at common times and use source 2).  With ODEF_SAVE_FINAL source 0
+ * summarises the one record.  odef_kernel_time_ms / odef_kernel_name report the last reduction as which = 2. */
+typedef enum {
+  ODEF_S_BASE = 64,
+  ODEF_S_FILTER_COUNT = 64,
+  ODEF_S_FILTER_MEAN = 65,
+  ODEF_S_FILTER_COV_WITHIN = 66,
+  ODEF_S_FILTER_COV_BETWEEN = 67,
+  ODEF_S_SMOOTH_COUNT = 72,
+  ODEF_S_SMOOTH_MEAN = 73,
+  ODEF_S_SMOOTH_COV_WITHIN = 74,
+  ODEF_S_SMOOTH_COV_BETWEEN = 75,
+  ODEF_S_DENSE_COUNT = 80,
+  ODEF_S_DENSE_MEAN = 81,
+  ODEF_S_DENSE_COV_WITHIN = 82,
+  ODEF_S_DENSE_COV_BETWEEN = 83
+} odef_summary_field;
 
 /* POD mirror of the reference's keyword structs (src/algorithms.jl:23-28,46-51) plus the
  * ensemble shape.  Zero-initialise, set struct_size = sizeof(odef_config). */
@@ -253,7 +288,7 @@ int odef_get_device(odef_ctx* ctx, int field, void** dev_ptr, size_t* bytes);
 int odef_bind_device(odef_ctx* ctx, int field, void* dev_ptr, size_t bytes);
 int odef_synchronize(odef_ctx* ctx);
 
-/* Device time of the last filter (which=0) / smoother (which=1) launch, measured with
+/* Device time of the last filter (which=0) / smoother (which=1) / ensemble-summary (which=2) launch, measured with
  * hipEvents on the launch stream; n_launches = kernels launched by that call. */
 int odef_kernel_time_ms(odef_ctx* ctx, int which, float* ms, int* n_launches);
 /* Name of the kernel that call launched (the dominant one of a multi-kernel pass), as a profiler prints it, e.g.

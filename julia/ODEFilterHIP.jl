@@ -30,6 +30,21 @@ const F_SAMPLES = 16
 # IEKS (src/ieks.jl): the algorithm id and the field of linearisation points [n_save][d][N] (include/odefilter.h)
 const ODEF_IEKS = 2
 const F_LINEARIZE_AT = 17
+# ensemble summary per time (odef_summary_field, include/odefilter.h): id = S_BASE + 8 * source + quantity, source 0 filter /
+# 1 smoothed / 2 dense records, quantity 0 COUNT / 1 MEAN / 2 COV_WITHIN / 3 COV_BETWEEN.  UNTESTED like the rest of this file.
+const S_BASE = 64
+const S_FILTER_COUNT = 64
+const S_FILTER_MEAN = 65
+const S_FILTER_COV_WITHIN = 66
+const S_FILTER_COV_BETWEEN = 67
+const S_SMOOTH_COUNT = 72
+const S_SMOOTH_MEAN = 73
+const S_SMOOTH_COV_WITHIN = 74
+const S_SMOOTH_COV_BETWEEN = 75
+const S_DENSE_COUNT = 80
+const S_DENSE_MEAN = 81
+const S_DENSE_COV_WITHIN = 82
+const S_DENSE_COV_BETWEEN = 83
 const RETCODES = (:Success, :MaxIters, :DtLessThanMin, :Unstable, :Unstable)
 
 """Ensemble algorithm: all trajectories of an `EnsembleProblem` on one GPU (`devices` empty / one entry) or sharded
@@ -44,7 +59,7 @@ end
 EnsembleHIP(rhs::Symbol; device=-1, devices=Int32[]) = EnsembleHIP(device, rhs, collect(Int32, devices))
 
 lasterr(ctx) = unsafe_string(ccall((:odef_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx))
-# which kernel the last filter (0) / smoother (1) pass launched, and its device time in ms
+# which kernel the last filter (0) / smoother (1) / ensemble-summary (2) pass launched, and its device time in ms
 function kernel_name(ctx, which::Integer)
     buf = zeros(UInt8, 256)
     GC.@preserve buf ccall((:odef_kernel_name, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{UInt8}, Csize_t), ctx, which, buf, length(buf))
@@ -62,6 +77,51 @@ function fetch(ctx, field, ::Type{T}, dims...) where {T}
     GC.@preserve out check(ccall((:odef_get, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Csize_t),
                                  ctx, field, out, sizeof(out)), ctx)
     out
+end
+
+"""
+    ensemble_summary(ctx, d; source=0) -> (n, mean, within, between)
+
+Per-time summary of the ensemble held by the live context `ctx` (state dimension of the ODE `d`), reduced on the device:
+`n[s]` included trajectories (Success retcode, finite mean), `mean[:, s]` the mean of their posterior means, `within[:, s]` /
+`between[:, s]` the packed lower triangles (element (k,l), k >= l, 0-based, at k(k+1)/2+l) of the mean posterior covariance and
+of the covariance of the means (divisor n).  `within + between` is the covariance of the equal-weight Gaussian mixture.
+source 0: filter records, 1: smoothed records, 2: the last `odef_dense_output` result (the only one an adaptive solve admits).
+"""
+function ensemble_summary(ctx, d::Integer; source::Integer=0)
+    id(q) = S_BASE + 8 * source + q
+    nb = Ref{Csize_t}(0)
+    check(ccall((:odef_field_bytes, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Csize_t}), ctx, id(0), nb), ctx)
+    n_t = Int(nb[] ÷ 8); tri = d * (d + 1) ÷ 2
+    return (n = fetch(ctx, id(0), Int64, n_t), mean = fetch(ctx, id(1), Float64, d, n_t),
+            within = fetch(ctx, id(2), Float64, tri, n_t), between = fetch(ctx, id(3), Float64, tri, n_t))
+end
+
+"""
+    merge_moments(parts) -> (n, mean, within, between)
+
+Exact pooled combination of per-shard `ensemble_summary` results (shards with n = 0 at a time are skipped there):
+n = sum n_r, mean = sum n_r mean_r / n, W = sum n_r W_r / n, B = sum n_r (B_r + (mean_r - mean)(mean_r - mean)') / n.
+"""
+function merge_moments(parts)
+    d, n_t = size(parts[1].mean); tri = size(parts[1].within, 1)
+    n = sum(p.n for p in parts)
+    mean = fill(NaN, d, n_t); within = fill(NaN, tri, n_t); between = fill(NaN, tri, n_t)
+    for s in 1:n_t
+        n[s] == 0 && continue
+        live = [p for p in parts if p.n[s] > 0]
+        mean[:, s] = sum(p.n[s] .* p.mean[:, s] for p in live) ./ n[s]
+        within[:, s] = sum(p.n[s] .* p.within[:, s] for p in live) ./ n[s]
+        acc = zeros(tri)
+        for p in live
+            dm = p.mean[:, s] .- mean[:, s]
+            for k in 0:d-1, l in 0:k
+                acc[k * (k + 1) ÷ 2 + l + 1] += p.n[s] * (p.between[k * (k + 1) ÷ 2 + l + 1, s] + dm[k + 1] * dm[l + 1])
+            end
+        end
+        between[:, s] = acc ./ n[s]
+    end
+    return (n = n, mean = mean, within = within, between = between)
 end
 
 """
@@ -235,7 +295,12 @@ function solve_sharded(eprob::DiffEqBase.EnsembleProblem, alg::Union{EK0,EK1}, e
             ccall((:odef_group_shard, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Int64}, Ptr{Int64}), g, k, first, count)
             (first[] + 1):(first[] + count[])      # 1-based trajectory range of shard k
         end
-        return (final_mean = final_mean, u_final = view(final_mean, :, 1:d), shards = shards)
+        # ensemble summary of the WHOLE ensemble on a fixed grid: every shard reduces its records on its own device, the
+        # per-shard blocks (kilobytes) are pooled on the host -- no collective, no full time-series gather
+        summary = adaptive ? nothing :
+            merge_moments([ensemble_summary(ccall((:odef_group_ctx, LIB), Ptr{Cvoid}, (Ptr{Cvoid}, Int32), g, k), d; source = alg.smooth ? 1 : 0)
+                           for k in 0:G-1])
+        return (final_mean = final_mean, u_final = view(final_mean, :, 1:d), shards = shards, summary = summary)
     finally
         ccall((:odef_group_destroy, LIB), Cvoid, (Ptr{Cvoid},), g)
     end

@@ -17,6 +17,7 @@
 #include "../../include/odefilter.h"
 #include "jit.h"
 #include "launch.h"
+#include "summary.h"
 
 using namespace odef;
 
@@ -72,9 +73,10 @@ struct odef_ctx {
   size_t ws_cap = 0;
   Buf f[ODEF_F_COUNT_];
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  float ms[2] = {0.f, 0.f};
-  int nl[2] = {0, 0};
-  char kname[2][192] = {"", ""};  // kernel of the last filter / smoother pass (odef_kernel_name)
+  float ms[3] = {0.f, 0.f, 0.f};
+  int nl[3] = {0, 0, 0};
+  char kname[3][192] = {"", "", ""};  // kernel of the last filter / smoother / ensemble-summary pass (odef_kernel_name)
+  SummaryState summary;  // cached ensemble summaries of the filter, smoothed and dense records (odef_summary_field)
   // odef_group runs its shards concurrently: with `defer` set, odef_solve_* / odef_smooth return after the launch and
   // complete_pending() does the wait + timing (pending: 1 = filter, 2 = smoother)
   bool defer = false;
@@ -82,7 +84,7 @@ struct odef_ctx {
   // IEKS: ODEF_F_LINEARIZE_AT was filled by odef_smooth (an owned buffer) from the fixed-grid solve on `lin_grid`
   bool lin_set = false;
   std::vector<double> lin_grid;
-  std::string err;
+  mutable std::string err;
 };
 
 namespace {
@@ -104,7 +106,7 @@ void clear_lin(odef_ctx* c) {
   c->lin_grid.clear();
 }
 
-int fail(odef_ctx* c, const char* fmt, ...) {
+int fail(const odef_ctx* c, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -241,6 +243,66 @@ size_t ensure_stage(odef_ctx* c, long want_recs, size_t per_rec_doubles) {
 
 int set_device(odef_ctx* c) {
   HIPCHK(c, hipSetDevice(c->device));
+  return 0;
+}
+
+// odef_summary_field: id = ODEF_S_BASE + 8 source + quantity
+bool is_summary_field(int field) {
+  return field >= ODEF_S_BASE && field < ODEF_S_BASE + 8 * 3 && (field - ODEF_S_BASE) % 8 < 4;
+}
+void invalidate_summary(odef_ctx* c, int source) { c->summary.src[source].valid = false; }
+void invalidate_summaries(odef_ctx* c) {
+  for (int k = 0; k < 3; ++k) invalidate_summary(c, k);
+}
+
+// number of times of a summary source, or -1 with the reason in odef_last_error
+long summary_times(const odef_ctx* c, int source, const char* who) {
+  if (!c->solved) return fail(c, "%s: ensemble summary requested before a solve (call odef_solve_* first)", who);
+  if (source == 2) {
+    if (!c->f[ODEF_F_DENSE_MEAN].valid || c->n_q < 1)
+      return fail(c, "%s: ensemble summary of source 2 needs odef_dense_output (or odef_dense_sample) first", who);
+    return c->n_q;
+  }
+  if (c->adaptive)
+    return fail(c, "%s: the records of one save index of an adaptive solve lie at different times per trajectory; "
+                   "evaluate odef_dense_output at common times and use source 2", who);
+  if (source == 1 && !c->smoothed_done) return fail(c, "%s: ensemble summary of the smoothed records needs odef_smooth first", who);
+  return c->n_save;
+}
+
+size_t summary_bytes(const odef_ctx* c, int quantity, long n_t) {
+  const size_t tri = (size_t)c->d * (c->d + 1) / 2;
+  return (size_t)n_t * 8 * (quantity == 0 ? 1 : quantity == 1 ? (size_t)c->d : tri);
+}
+
+// the cached array of a summary field; the first request after the source's records changed runs the reduction
+int summary_field(odef_ctx* c, int field, const char* who, void** ptr, size_t* bytes) {
+  const int source = (field - ODEF_S_BASE) / 8, quantity = (field - ODEF_S_BASE) % 8;
+  const long n_t = summary_times(c, source, who);
+  if (n_t < 0) return -1;
+  if (set_device(c)) return -1;
+  SummaryCache& sc = c->summary.src[source];
+  if (!sc.valid || sc.n_t != n_t) {
+    static const int kMean[3] = {ODEF_F_MEAN, ODEF_F_SMOOTH_MEAN, ODEF_F_DENSE_MEAN};
+    static const int kCov[3] = {ODEF_F_COV_TRIL, ODEF_F_SMOOTH_COV_TRIL, ODEF_F_DENSE_COV_TRIL};
+    SummaryArgs a;
+    a.mean = (const double*)c->f[kMean[source]].ptr;
+    a.cov = (const double*)c->f[kCov[source]].ptr;
+    a.retcode = (const int*)c->f[ODEF_F_RETCODE].ptr;
+    a.N = c->cfg.n_traj;
+    a.n_t = n_t;
+    a.d = c->d;
+    a.D = c->D;
+    a.TRI = c->TRI;
+    if (!a.mean || !a.cov || !a.retcode) return fail(c, "%s: the records of summary source %d hold no data", who, source);
+    std::string err;
+    int walk = 0;
+    if (summary_run(c->summary, sc, a, c->stream, &c->ms[2], &c->nl[2], &walk, err)) return fail(c, "%s: %s", who, err.c_str());
+    std::snprintf(c->kname[2], sizeof c->kname[2], "odef::summary_sums_kernel<%d>", walk);
+  }
+  void* const p[4] = {sc.count, sc.mean, sc.within, sc.between};
+  *ptr = p[quantity];
+  *bytes = summary_bytes(c, quantity, n_t);
   return 0;
 }
 
@@ -453,6 +515,7 @@ void odef_destroy(odef_ctx* c) {
   if (c->d_tgrid) (void)hipFree(c->d_tgrid);
   if (c->d_tq) (void)hipFree(c->d_tq);
   if (c->d_tab_idx) (void)hipFree(c->d_tab_idx);
+  summary_free(c->summary);
   for (int k = 0; k < 4; ++k)
     if (c->ev[k]) (void)hipEventDestroy(c->ev[k]);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -490,6 +553,7 @@ int odef_set_problem(odef_ctx* c, const double* u0, const double* p, double t0) 
   c->t0 = t0;
   c->have_problem = true;
   clear_lin(c);
+  invalidate_summaries(c);
   return 0;
 }
 
@@ -504,6 +568,7 @@ int odef_set_problem_device(odef_ctx* c, const double* d_u0, const double* d_p, 
   c->t0 = t0;
   c->have_problem = true;
   clear_lin(c);
+  invalidate_summaries(c);
   return 0;
 }
 
@@ -525,6 +590,7 @@ int odef_set_problem_perturbed(odef_ctx* c, const double* base_u0, const double*
   c->t0 = t0;
   c->have_problem = true;
   clear_lin(c);
+  invalidate_summaries(c);
   return 0;
 }
 
@@ -602,6 +668,7 @@ static int finish_filter(odef_ctx* c, int nlaunch) {
   c->nl[0] = nlaunch;
   c->solved = true;
   c->smoothed_done = false;
+  invalidate_summaries(c);
   c->pending = 1;
   return c->defer ? 0 : complete_pending(c);
 }
@@ -820,6 +887,7 @@ int odef_smooth(odef_ctx* c) {
   }
   c->nl[1] = 1;
   c->smoothed_done = true;
+  invalidate_summary(c, 1);
   c->pending = 2;
   return c->defer ? 0 : complete_pending(c);
 }
@@ -841,6 +909,7 @@ int odef_dense_output(odef_ctx* c, const double* tq, int64_t n_q, int smoothed) 
   HIPCHK(c, hipMemcpyAsync(c->d_tq, tq, sizeof(double) * n_q, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->n_q = (long)n_q;
+  invalidate_summary(c, 2);
   const size_t N = (size_t)c->cfg.n_traj;
   if (ensure(c, ODEF_F_DENSE_MEAN, (size_t)n_q * c->D * N * sizeof(double))) return -1;
   if (ensure(c, ODEF_F_DENSE_COV_TRIL, (size_t)n_q * c->TRI * N * sizeof(double))) return -1;
@@ -935,6 +1004,12 @@ int odef_dense_sample(odef_ctx* c, const double* tq, int64_t n_q, int64_t n_samp
 int64_t odef_n_save(const odef_ctx* c) { return c ? c->n_save : -1; }
 
 int odef_field_bytes(const odef_ctx* c, int field, size_t* bytes) {
+  if (c && bytes && is_summary_field(field)) {
+    const long n_t = summary_times(c, (field - ODEF_S_BASE) / 8, "odef_field_bytes");
+    if (n_t < 0) return -1;
+    *bytes = summary_bytes(c, (field - ODEF_S_BASE) % 8, n_t);
+    return 0;
+  }
   if (!c || !bytes || field < 0 || field >= ODEF_F_COUNT_) return -1;
   if (field == ODEF_F_T && !c->adaptive) { *bytes = c->tgrid.size() ? (size_t)c->n_save * sizeof(double) : 0; return 0; }
   *bytes = c->f[field].valid;
@@ -943,6 +1018,15 @@ int odef_field_bytes(const odef_ctx* c, int field, size_t* bytes) {
 
 int odef_get(odef_ctx* c, int field, void* host_dst, size_t bytes) {
   if (!c || !host_dst) return fail(c, "odef_get: null argument");
+  if (is_summary_field(field)) {
+    void* src = nullptr;
+    size_t have = 0;
+    if (summary_field(c, field, "odef_get", &src, &have)) return -1;
+    if (bytes != have) return fail(c, "odef_get: field %d holds %zu bytes, caller asked for %zu", field, have, bytes);
+    HIPCHK(c, hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+  }
   if (field < 0 || field >= ODEF_F_COUNT_) return fail(c, "odef_get: unknown field %d", field);
   if (set_device(c)) return -1;
   if (field == ODEF_F_T && !c->adaptive) {
@@ -963,6 +1047,7 @@ int odef_get(odef_ctx* c, int field, void* host_dst, size_t bytes) {
 
 int odef_get_device(odef_ctx* c, int field, void** dev_ptr, size_t* bytes) {
   if (!c || !dev_ptr || !bytes) return fail(c, "odef_get_device: null argument");
+  if (is_summary_field(field)) return summary_field(c, field, "odef_get_device", dev_ptr, bytes);
   if (field < 0 || field >= ODEF_F_COUNT_) return fail(c, "odef_get_device: unknown field %d", field);
   const Buf& b = c->f[field];
   if (!b.ptr || !b.valid) return fail(c, "odef_get_device: field %d holds no data yet", field);
@@ -1000,13 +1085,13 @@ int odef_synchronize(odef_ctx* c) {
 }
 
 int odef_kernel_name(odef_ctx* c, int which, char* buf, size_t n) {
-  if (!c || which < 0 || which > 1 || !buf || n == 0) return -1;
+  if (!c || which < 0 || which > 2 || !buf || n == 0) return -1;
   std::snprintf(buf, n, "%s", c->kname[which]);
   return 0;
 }
 
 int odef_kernel_time_ms(odef_ctx* c, int which, float* ms, int* n_launches) {
-  if (!c || which < 0 || which > 1 || !ms) return -1;
+  if (!c || which < 0 || which > 2 || !ms) return -1;
   *ms = c->ms[which];
   if (n_launches) *n_launches = c->nl[which];
   return 0;

@@ -48,3 +48,20 @@ def gathered_to_global(g: torch.Tensor) -> torch.Tensor:
     """[world, K, n_local] -> [K, world*n_local] in global trajectory order."""
     w, k, n = g.shape
     return g.permute(1, 0, 2).reshape(k, w * n)
+
+
+def allgather_moments(moments, world: int):
+    """One all_gather of a rank's ensemble-summary block (count [n_t], mean [n_t, d], within and between [n_t, tri]; a few
+    kilobytes, so host memory and any backend): the list of every rank's (count, mean, within, between), in rank order, for
+    `host.merge_moments`.  Counts travel as doubles (exact below 2^53).  With the "nccl" backend the block goes through the
+    rank's current GPU, since RCCL moves device memory only."""
+    import numpy as np
+
+    n, m, w, b = moments
+    if world == 1:
+        return [moments]
+    n_t, d, tri = m.shape[0], m.shape[1], w.shape[1]
+    flat = np.concatenate([np.asarray(n, float).reshape(n_t, 1), m, w, b], axis=1)  # [n_t, 1 + d + 2 tri]
+    dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+    g = allgather_shards(torch.from_numpy(np.ascontiguousarray(flat)).to(dev), world).cpu().numpy()
+    return [(g[r, :, 0].astype(np.int64), g[r, :, 1:1 + d], g[r, :, 1 + d:1 + d + tri], g[r, :, 1 + d + tri:]) for r in range(world)]

@@ -36,6 +36,28 @@ RETCODES = {0: "Success", 1: "MaxIters", 2: "DtLessThanMin", 3: "Unstable", 4: "
  F_SMOOTH_MEAN, F_SMOOTH_COV_TRIL, F_U0, F_DENSE_MEAN, F_DENSE_COV_TRIL, F_SAMPLES, F_LINEARIZE_AT) = range(18)
 ODEF_F_LINEARIZE_AT = F_LINEARIZE_AT  # IEKS linearisation points [n_save][d][N] (include/odefilter.h)
 _INT_FIELDS = {F_NACCEPT, F_NREJECT, F_NF, F_NJAC, F_NSAVED, F_RETCODE}
+# ensemble summary per time (odef_summary_field, include/odefilter.h): id = S_BASE + 8 * source + quantity
+S_BASE = 64
+S_SOURCE_FILTER, S_SOURCE_SMOOTH, S_SOURCE_DENSE = 0, 1, 2
+S_COUNT, S_MEAN, S_COV_WITHIN, S_COV_BETWEEN = 0, 1, 2, 3
+SUMMARY_FIELDS = {
+    "ODEF_S_BASE": 64,
+    "ODEF_S_FILTER_COUNT": 64, "ODEF_S_FILTER_MEAN": 65, "ODEF_S_FILTER_COV_WITHIN": 66, "ODEF_S_FILTER_COV_BETWEEN": 67,
+    "ODEF_S_SMOOTH_COUNT": 72, "ODEF_S_SMOOTH_MEAN": 73, "ODEF_S_SMOOTH_COV_WITHIN": 74, "ODEF_S_SMOOTH_COV_BETWEEN": 75,
+    "ODEF_S_DENSE_COUNT": 80, "ODEF_S_DENSE_MEAN": 81, "ODEF_S_DENSE_COV_WITHIN": 82, "ODEF_S_DENSE_COV_BETWEEN": 83,
+}
+
+
+def summary_field(source: int, quantity: int) -> int:
+    """Field id of an ensemble-summary array: source 0 filter / 1 smoothed / 2 dense records, quantity 0 COUNT / 1 MEAN /
+    2 COV_WITHIN / 3 COV_BETWEEN."""
+    if source not in (0, 1, 2) or quantity not in (0, 1, 2, 3):
+        raise OdefError(f"no ensemble-summary field for source {source}, quantity {quantity}")
+    return S_BASE + 8 * source + quantity
+
+
+def _is_summary_field(f: int) -> bool:
+    return S_BASE <= f < S_BASE + 24 and (f - S_BASE) % 8 < 4
 MAX_ORDER = 5
 
 
@@ -250,6 +272,33 @@ class DeviceGroup:
             parts.append(out)
         return np.concatenate(parts, axis=-1)
 
+    def ensemble_moments(self, source: int):
+        """Ensemble summary of the WHOLE ensemble: every shard reduces its own records on its device (`odef_summary_field`),
+        the per-shard blocks (kilobytes) are pooled on the host with `merge_moments`.  Returns (count, mean, within, between)."""
+        parts = []
+        for g in range(self.G):
+            c = self.lib.odef_group_ctx(self._h, g)
+            blk = []
+            for qty in range(4):
+                f = summary_field(source, qty)
+                b = C.c_size_t()
+                self._chk_ctx(g, self.lib.odef_field_bytes(c, f, C.byref(b)))
+                out = np.empty(b.value // 8, dtype=np.int64 if qty == S_COUNT else np.float64)
+                self._chk_ctx(g, self.lib.odef_get(c, f, out.ctypes.data_as(_vp), b.value))
+                blk.append(out if qty == S_COUNT else out.reshape(len(blk[0]), -1))
+            parts.append(tuple(blk))
+        return merge_moments(parts)
+
+    def summary(self, smoothed: bool = False) -> "EnsembleSummary":
+        """`EnsembleSummary` of the whole ensemble on the save grid of a fixed-grid solve."""
+        n, m, w, b = self.ensemble_moments(S_SOURCE_SMOOTH if smoothed else S_SOURCE_FILTER)
+        c = self.lib.odef_group_ctx(self._h, 0)
+        nb = C.c_size_t()
+        self._chk_ctx(0, self.lib.odef_field_bytes(c, F_T, C.byref(nb)))
+        t = np.empty(nb.value // 8)
+        self._chk_ctx(0, self.lib.odef_get(c, F_T, t.ctypes.data_as(_vp), nb.value))
+        return EnsembleSummary.from_moments(t, n, m, w, b)
+
     def shard_kernel_ms(self, which=0):
         ms = []
         for g in range(self.G):
@@ -413,8 +462,13 @@ class Context:
         """Field in the device layout (include/odefilter.h), as a flat numpy array reshaped."""
         nbytes = self.field_bytes(f)
         dt = np.int32 if f in _INT_FIELDS else np.float64
+        if _is_summary_field(f):  # [n_t] int64 counts, [n_t, d] means, [n_t, d(d+1)/2] packed covariances
+            dt = np.int64 if (f - S_BASE) % 8 == S_COUNT else np.float64
         out = np.empty(nbytes // np.dtype(dt).itemsize, dtype=dt)
         self._chk(self.lib.odef_get(self._h, f, out.ctypes.data_as(_vp), nbytes))
+        if _is_summary_field(f):
+            qty = (f - S_BASE) % 8
+            return out if qty == S_COUNT else out.reshape(-1, self.d if qty == S_MEAN else self.d * (self.d + 1) // 2)
         ns, N = self.n_save, self.N
         if f in (F_MEAN, F_SMOOTH_MEAN):
             return out.reshape(ns, self.D, N)
@@ -430,6 +484,12 @@ class Context:
             return out.reshape(-1, self.d, N)
         return out
 
+    def ensemble_moments(self, source: int):
+        """Ensemble summary per time of the filter (0), smoothed (1) or last dense-output (2) records, reduced on the device
+        (`odef_summary_field`): (count [n_t] int64, mean [n_t, d], within [n_t, tri], between [n_t, tri]), tri = d(d+1)/2 packed
+        lower triangles.  The first request after the records changed launches the reduction; later ones read the cache."""
+        return tuple(self.get(summary_field(source, qty)) for qty in range(4))
+
     def device_ptr(self, f: int):
         p, b = _vp(), C.c_size_t()
         self._chk(self.lib.odef_get_device(self._h, f, C.byref(p), C.byref(b)))
@@ -439,7 +499,7 @@ class Context:
         self._chk(self.lib.odef_bind_device(self._h, f, _vp(ptr), nbytes))
 
     def kernel_name(self, which=0) -> str:
-        """Name of the kernel the last filter (0) / smoother (1) pass launched, as a profiler prints it."""
+        """Name of the kernel the last filter (0) / smoother (1) / ensemble-summary (2) pass launched, as a profiler prints it."""
         buf = C.create_string_buffer(256)
         self._chk(self.lib.odef_kernel_name(self._h, which, buf, 256))
         return buf.value.decode()
@@ -666,6 +726,54 @@ def unpack_tril(c: np.ndarray, D: int) -> np.ndarray:
     return out
 
 
+def merge_moments(parts):
+    """Exact pooled combination of per-shard ensemble summaries.  parts: iterable of (n [n_t], mean [n_t, d], within [n_t, tri],
+    between [n_t, tri]); shards with n = 0 at a time are skipped there.  n = sum n_r, mean = sum n_r mean_r / n, W = sum n_r W_r / n,
+    B = sum n_r (B_r + (mean_r - mean)(mean_r - mean)') / n; with n = 0 the moments are NaN.  Pure numpy."""
+    parts = [(np.asarray(n, np.int64), np.asarray(m, float), np.asarray(w, float), np.asarray(b, float)) for n, m, w, b in parts]
+    if not parts:
+        raise OdefError("merge_moments: no parts")
+    n_t, d = parts[0][1].shape
+    il = np.tril_indices(d)
+    n = sum(p[0] for p in parts)
+    nn = np.where(n > 0, n, 1).astype(float)[:, None]
+    wgt = [(p[0] / nn[:, 0])[:, None] for p in parts]  # n_r / n
+    mean = sum(np.where(p[0][:, None] > 0, w_r * p[1], 0.0) for p, w_r in zip(parts, wgt))
+    within = sum(np.where(p[0][:, None] > 0, w_r * p[2], 0.0) for p, w_r in zip(parts, wgt))
+    between = np.zeros_like(within)
+    for p, w_r in zip(parts, wgt):
+        dm = np.where(p[0][:, None] > 0, p[1] - mean, 0.0)
+        between += np.where(p[0][:, None] > 0, w_r * (p[3] + dm[:, il[0]] * dm[:, il[1]]), 0.0)
+    empty = (n == 0)[:, None]
+    return n, np.where(empty, np.nan, mean), np.where(empty, np.nan, within), np.where(empty, np.nan, between)
+
+
+@dataclass
+class EnsembleSummary:
+    """Per-time summary of an ensemble: the equal-weight mixture of the trajectories' Gaussian posteriors has mean `mean` and
+    covariance `cov` = `cov_within` (mean posterior covariance) + `cov_between` (covariance of the posterior means, divisor n).
+    `n` counts the trajectories included at each time (Success retcode, finite mean); with n = 0 the moments are NaN."""
+    t: np.ndarray            # [n_t]
+    n: np.ndarray            # [n_t] int64
+    mean: np.ndarray         # [n_t, d]
+    cov_within: np.ndarray   # [n_t, d, d]
+    cov_between: np.ndarray  # [n_t, d, d]
+
+    @classmethod
+    def from_moments(cls, t, n, mean, within, between):
+        d = mean.shape[1]
+        return cls(np.asarray(t, float).reshape(-1), n, mean, unpack_tril(within, d), unpack_tril(between, d))
+
+    @property
+    def cov(self) -> np.ndarray:
+        return self.cov_within + self.cov_between
+
+    @property
+    def std(self) -> np.ndarray:
+        """[n_t, d]: square root of the diagonal of `cov`."""
+        return np.sqrt(np.diagonal(self.cov, axis1=1, axis2=2))
+
+
 @dataclass
 class DEStats:
     nf: np.ndarray
@@ -796,6 +904,29 @@ class EnsembleSolution:
         sm = self.smoothed if smoothed is None else smoothed
         m, c = self.ctx.dense_output(tq, sm)
         return m.transpose(2, 0, 1), unpack_tril(c.transpose(2, 0, 1), self.D)
+
+    def summary(self, t=None, smoothed: Optional[bool] = None) -> EnsembleSummary:
+        """Mean path of the ensemble and its uncertainty, reduced on the device (`odef_summary_field`): nothing but the four
+        small arrays crosses to the host.  t = None: the save grid of a fixed-grid solve, smoothed when the solution is (the rule
+        of `sol.u`).  With t: the dense output `sol(t)` is evaluated on the device and summarised.  Adaptive solves need t (their
+        records of one save index lie at different times per trajectory).  A distributed solve returns the summary of the WHOLE
+        ensemble on every rank: one all_gather of the per-shard blocks, pooled with `merge_moments`."""
+        sm = self.smoothed if smoothed is None else bool(smoothed)
+        if t is None:
+            if self.adaptive:
+                raise OdefError("summary(): an adaptive solve keeps its records at different times per trajectory; "
+                                "pass common times t (the dense output is summarised)")
+            tt = self.t
+            moments = self.ctx.ensemble_moments(S_SOURCE_SMOOTH if sm else S_SOURCE_FILTER)
+        else:
+            tt = np.ascontiguousarray(np.atleast_1d(np.asarray(t, float)))
+            self.ctx._chk(self.ctx.lib.odef_dense_output(self.ctx._h, _as_dp(tt), len(tt), int(sm)))
+            moments = self.ctx.ensemble_moments(S_SOURCE_DENSE)
+        if self.shard is not None and self.shard[3] > 1:
+            from . import dist as od
+
+            moments = merge_moments(od.allgather_moments(moments, self.shard[3]))
+        return EnsembleSummary.from_moments(tt, *moments)
 
     def sample_states(self, n: int = 1, seed: int = 0x5A3B1E, noise_scale: float = 1.0) -> np.ndarray:
         """`sample_states(sol, n)` (src/solution_sampling.jl:15-18, 24-62): [N, n_save, D, n] joint draws of the

@@ -28,3 +28,5 @@ E.emul_solve(fh.rhs_id, 2, 1, False, fh.u0[None, :], fh.p, tgrid=np.arange(9) * 
 print("sanitized emulation run: clean")
 PY
 LD_PRELOAD=$(g++ -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 python /tmp/odef_san_run.py
+# the ensemble-summary reduction (tests/emul/emul_summary.cpp), every case of its emulation test
+ODEF_EMUL_SANITIZE=1 LD_PRELOAD=$(g++ -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 python -m pytest tests/test_summary_emul.py -q -p no:cacheprovider
