@@ -34,6 +34,7 @@
  *   odef_smooth_step                predict!, update!, smooth (pure functions)   src/filtering.jl:17,79,136
  *   odef_ibm / odef_preconditioner  ibm(d,q), preconditioner(T,d,q)              src/priors.jl:7-59,
  *                                                                                src/preconditioning.jl:1-17
+ *   odef_errors_field ids           sol.errors, sol.u_analytic                    src/solution.jl:10-11,68-74,129-130
  *   odef_summary_field ids          nothing in the reference: per-time mean and covariance of the ensemble's Gaussian mixture,
  *                                   reduced on the device and read with odef_get (see odef_summary_field)
  *   odef_group_* / odef_allgather   nothing in the reference (it has no ensemble and no distributed code):
@@ -171,6 +172,48 @@ typedef enum {
   ODEF_S_DENSE_COV_BETWEEN = 83
 } odef_summary_field;
 
+/* Solution errors per trajectory, reduced on the device: sol.errors and sol.u_analytic of the reference (src/solution.jl:10-11,
+ * 68-74, 129-130; test/specific_problems.jl:25-37).  For trajectory i over its own saves k = 0..n-1, e_k = u_k - u*_k in R^d with u_k
+ * rows 0..d-1 of the mean and Sigma_k the d x d solution block of the covariance:
+ *   FINAL       mean_a |e_{n-1,a}|                              double [N]   (DiffEqBase calculate_solution_errors!, :final)
+ *   L2          sqrt(mean_{k,a} e_{k,a}^2)                      double [N]   (:l2)
+ *   LINF        max_{k,a} |e_{k,a}|                             double [N]   (:l-infinity)
+ *   CHI2        mean_k e_k' Sigma_k^+ e_k / d                   double [N]   nothing in the reference: ~ 1 for a calibrated posterior.
+ *                                                               Saves whose block is exactly zero (the initial record; u' = 0) are
+ *                                                               left out; NaN when none is left.  A non-positive pivot of the
+ *                                                               factorisation drops its direction.
+ *   NUSED       number of saves in L2 / LINF                    int64  [N]   adaptive solves: the zero-length repeats of rejected
+ *                                                               attempts are skipped, NUSED = accepted steps + 1
+ *   U_ANALYTIC  u* at the trajectory's own save times           double [n_save][d][N], computed when asked for
+ * Field id = ODEF_E_BASE + 8 * source + quantity, source 0: the filter records, 1: the smoothed records (the reference's sol.u after
+ * smooth = true).  odef_field_bytes, odef_get and odef_get_device accept these ids.  The truth u* comes from
+ *   (a) the vector field's `analytic(u0, p, t, out)` member (ODEF_RHS_LINEAR has one; a run-time compiled field may), or
+ *   (b) a reference buffer [n_save][d][N] in device memory bound with odef_bind_device(ctx, ODEF_E_REFERENCE, ptr, bytes) -- read
+ *       only, never written, fixed grids only; (ptr = NULL lets it go).  A bound reference takes precedence; U_ANALYTIC is then
+ *       that buffer.
+ * The first request for a source runs the pass on the context's stream (deterministic, no floating-point atomics: two requests
+ * agree bit for bit) and caches the five small arrays; odef_solve_*, odef_smooth (source 1), odef_set_problem* and the bind of
+ * ODEF_E_REFERENCE invalidate them.  Refused with a message: before a solve, source 1 before odef_smooth, a field without
+ * `analytic` and nothing bound, a bound reference after an ADAPTIVE solve (per-trajectory times: use `analytic`).  A trajectory
+ * whose RETCODE is not Success still gets numbers over the saves it has; non-finite entries propagate as NaN.
+ * odef_kernel_time_ms / odef_kernel_name report the last pass as which = 3. */
+typedef enum {
+  ODEF_E_BASE = 128,
+  ODEF_E_FINAL = 128,
+  ODEF_E_L2 = 129,
+  ODEF_E_LINF = 130,
+  ODEF_E_CHI2 = 131,
+  ODEF_E_NUSED = 132,
+  ODEF_E_U_ANALYTIC = 133,
+  ODEF_E_SMOOTH_FINAL = 136,
+  ODEF_E_SMOOTH_L2 = 137,
+  ODEF_E_SMOOTH_LINF = 138,
+  ODEF_E_SMOOTH_CHI2 = 139,
+  ODEF_E_SMOOTH_NUSED = 140,
+  ODEF_E_SMOOTH_U_ANALYTIC = 141,
+  ODEF_E_REFERENCE = 144 /* odef_bind_device only */
+} odef_errors_field;
+
 /* POD mirror of the reference's keyword structs (src/algorithms.jl:23-28,46-51) plus the
  * ensemble shape.  Zero-initialise, set struct_size = sizeof(odef_config). */
 typedef struct {
@@ -211,6 +254,8 @@ const char* odef_last_error(const odef_ctx* ctx); /* ctx may be NULL: last error
  *       __device__ static void f(const T (&u)[3], const double* p, T (&du)[3]) { ... }
  *       __device__ static void jac(const double (&u)[3], const double* p, double (&J)[3][3]) { ... }  // optional:
  *           // without it EK1 differentiates f in forward mode (the reference's ForwardDiff fallback, :119-121)
+ *       template <class T>   // optional: the closed-form solution at the absolute time t (f.analytic); with it the
+ *       __device__ static void analytic(const T (&u0)[3], const double* p, T t, T (&out)[3]) { ... }  // odef_errors_field ids work
  *     };
  *
  * A hipcc child process ($ODEFILTER_HIP_HIPCC, else hipcc on PATH, else /opt/rocm/bin/hipcc) compiles the library's
@@ -288,7 +333,7 @@ int odef_get_device(odef_ctx* ctx, int field, void** dev_ptr, size_t* bytes);
 int odef_bind_device(odef_ctx* ctx, int field, void* dev_ptr, size_t bytes);
 int odef_synchronize(odef_ctx* ctx);
 
-/* Device time of the last filter (which=0) / smoother (which=1) / ensemble-summary (which=2) launch, measured with
+/* Device time of the last filter (which=0) / smoother (which=1) / ensemble-summary (which=2) / solution-error (which=3) launch, measured with
  * hipEvents on the launch stream; n_launches = kernels launched by that call. */
 int odef_kernel_time_ms(odef_ctx* ctx, int which, float* ms, int* n_launches);
 /* Name of the kernel that call launched (the dominant one of a multi-kernel pass), as a profiler prints it, e.g.

@@ -45,6 +45,23 @@ const S_DENSE_COUNT = 80
 const S_DENSE_MEAN = 81
 const S_DENSE_COV_WITHIN = 82
 const S_DENSE_COV_BETWEEN = 83
+# solution errors per trajectory (odef_errors_field, include/odefilter.h): id = E_BASE + 8 * source + quantity, source 0 filter /
+# 1 smoothed records, quantity 0 FINAL / 1 L2 / 2 LINF / 3 CHI2 / 4 NUSED / 5 U_ANALYTIC; E_REFERENCE is the bindable truth
+# [n_save][d][N] (odef_bind_device).  UNTESTED like the rest of this file.
+const E_BASE = 128
+const E_FINAL = 128
+const E_L2 = 129
+const E_LINF = 130
+const E_CHI2 = 131
+const E_NUSED = 132
+const E_U_ANALYTIC = 133
+const E_SMOOTH_FINAL = 136
+const E_SMOOTH_L2 = 137
+const E_SMOOTH_LINF = 138
+const E_SMOOTH_CHI2 = 139
+const E_SMOOTH_NUSED = 140
+const E_SMOOTH_U_ANALYTIC = 141
+const E_REFERENCE = 144
 const RETCODES = (:Success, :MaxIters, :DtLessThanMin, :Unstable, :Unstable)
 
 """Ensemble algorithm: all trajectories of an `EnsembleProblem` on one GPU (`devices` empty / one entry) or sharded
@@ -59,7 +76,7 @@ end
 EnsembleHIP(rhs::Symbol; device=-1, devices=Int32[]) = EnsembleHIP(device, rhs, collect(Int32, devices))
 
 lasterr(ctx) = unsafe_string(ccall((:odef_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx))
-# which kernel the last filter (0) / smoother (1) / ensemble-summary (2) pass launched, and its device time in ms
+# which kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) pass launched, and its device time in ms
 function kernel_name(ctx, which::Integer)
     buf = zeros(UInt8, 256)
     GC.@preserve buf ccall((:odef_kernel_name, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{UInt8}, Csize_t), ctx, which, buf, length(buf))
@@ -95,6 +112,21 @@ function ensemble_summary(ctx, d::Integer; source::Integer=0)
     n_t = Int(nb[] ÷ 8); tri = d * (d + 1) ÷ 2
     return (n = fetch(ctx, id(0), Int64, n_t), mean = fetch(ctx, id(1), Float64, d, n_t),
             within = fetch(ctx, id(2), Float64, tri, n_t), between = fetch(ctx, id(3), Float64, tri, n_t))
+end
+
+"""
+    solution_errors(ctx, n_traj; source=0) -> Dict(:l∞, :l2, :final, :chi2), nused
+
+`sol.errors` of every trajectory of the live context `ctx` (src/solution.jl:11, 68-74), reduced on the device against the vector
+field's `analytic` or the reference bound as `E_REFERENCE`: DiffEqBase's `:l∞`, `:l2`, `:final` of the solution part of the
+means, and `:chi2 = mean_k e' Sigma^+ e / d` (about 1 for a calibrated posterior), each of length `n_traj`.  source 0: filter
+records, 1: smoothed records.  UNTESTED.
+"""
+function solution_errors(ctx, n_traj::Integer; source::Integer=0)
+    id(q) = E_BASE + 8 * source + q
+    errs = Dict(:final => fetch(ctx, id(0), Float64, n_traj), :l2 => fetch(ctx, id(1), Float64, n_traj),
+                Symbol("l∞") => fetch(ctx, id(2), Float64, n_traj), :chi2 => fetch(ctx, id(3), Float64, n_traj))
+    return errs, fetch(ctx, id(4), Int64, n_traj)
 end
 
 """

@@ -18,6 +18,7 @@
 #include "jit.h"
 #include "launch.h"
 #include "summary.h"
+#include "errors.h"
 
 using namespace odef;
 
@@ -73,10 +74,13 @@ struct odef_ctx {
   size_t ws_cap = 0;
   Buf f[ODEF_F_COUNT_];
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  float ms[3] = {0.f, 0.f, 0.f};
-  int nl[3] = {0, 0, 0};
-  char kname[3][192] = {"", "", ""};  // kernel of the last filter / smoother / ensemble-summary pass (odef_kernel_name)
+  float ms[4] = {0.f, 0.f, 0.f, 0.f};
+  int nl[4] = {0, 0, 0, 0};
+  char kname[4][192] = {"", "", "", ""};  // kernel of the last filter / smoother / ensemble-summary / solution-error pass (odef_kernel_name)
   SummaryState summary;  // cached ensemble summaries of the filter, smoothed and dense records (odef_summary_field)
+  ErrorsState errors;    // cached solution errors of the filter and smoothed records (odef_errors_field)
+  const double* err_ref = nullptr;  // ODEF_E_REFERENCE: the bound truth [n_save][d][N] (caller memory, read only)
+  size_t err_ref_bytes = 0;
   // odef_group runs its shards concurrently: with `defer` set, odef_solve_* / odef_smooth return after the launch and
   // complete_pending() does the wait + timing (pending: 1 = filter, 2 = smoother)
   bool defer = false;
@@ -250,7 +254,11 @@ int set_device(odef_ctx* c) {
 bool is_summary_field(int field) {
   return field >= ODEF_S_BASE && field < ODEF_S_BASE + 8 * 3 && (field - ODEF_S_BASE) % 8 < 4;
 }
-void invalidate_summary(odef_ctx* c, int source) { c->summary.src[source].valid = false; }
+// (the records of `source` changed: its cached summary goes, and for the filter / smoothed records the cached solution errors)
+void invalidate_summary(odef_ctx* c, int source) {
+  c->summary.src[source].valid = false;
+  if (source < 2) c->errors.src[source].valid = c->errors.src[source].truth_valid = false;
+}
 void invalidate_summaries(odef_ctx* c) {
   for (int k = 0; k < 3; ++k) invalidate_summary(c, k);
 }
@@ -303,6 +311,82 @@ int summary_field(odef_ctx* c, int field, const char* who, void** ptr, size_t* b
   void* const p[4] = {sc.count, sc.mean, sc.within, sc.between};
   *ptr = p[quantity];
   *bytes = summary_bytes(c, quantity, n_t);
+  return 0;
+}
+
+// odef_errors_field: id = ODEF_E_BASE + 8 source + quantity (source 0 filter / 1 smoothed records)
+bool is_errors_field(int field) {
+  return field >= ODEF_E_BASE && field < ODEF_E_BASE + 8 * 2 && (field - ODEF_E_BASE) % 8 <= ODEF_E_U_ANALYTIC - ODEF_E_BASE;
+}
+
+size_t errors_bytes(const odef_ctx* c, int quantity) {
+  const size_t N = (size_t)c->cfg.n_traj;
+  return quantity == ODEF_E_U_ANALYTIC - ODEF_E_BASE ? (size_t)c->n_save * c->d * N * sizeof(double) : N * 8;
+}
+
+// 0 when the solution errors of `source` can be computed, else -1 with the reason in odef_last_error (no device is touched)
+int errors_check(const odef_ctx* c, int source, const char* who) {
+  if (!c->solved) return fail(c, "%s: solution errors requested before a solve (call odef_solve_* first)", who);
+  if (source == 1 && !c->smoothed_done) return fail(c, "%s: solution errors of the smoothed records need odef_smooth first", who);
+  if (!c->err_ref && !c->field->errors)
+    return fail(c, "%s: nothing to compare with: the vector field (rhs %d) has no `analytic` member and no reference is bound "
+                   "(odef_bind_device(ctx, ODEF_E_REFERENCE, [n_save][d][N], bytes))", who, c->cfg.rhs_id);
+  if (c->err_ref && c->adaptive)
+    return fail(c, "%s: a bound reference [n_save][d][N] belongs to a fixed grid; the saves of an adaptive solve lie at different times "
+                   "per trajectory: give the vector field an `analytic` member (and unbind ODEF_E_REFERENCE)", who);
+  const size_t need = (size_t)c->n_save * c->d * (size_t)c->cfg.n_traj * sizeof(double);
+  if (c->err_ref && c->err_ref_bytes < need)
+    return fail(c, "%s: the bound ODEF_E_REFERENCE buffer holds %zu bytes, the records need n_save * d * N * 8 = %zu", who,
+                c->err_ref_bytes, need);
+  return 0;
+}
+
+// the cached array of a solution-error field; the first request after the source's records (or the truth) changed runs the pass
+int errors_field(odef_ctx* c, int field, const char* who, void** ptr, size_t* bytes) {
+  const int source = (field - ODEF_E_BASE) / 8, quantity = (field - ODEF_E_BASE) % 8;
+  if (errors_check(c, source, who)) return -1;
+  if (set_device(c)) return -1;
+  ErrorsCache& ec = c->errors.src[source];
+  const bool truth = quantity == ODEF_E_U_ANALYTIC - ODEF_E_BASE;
+  *bytes = errors_bytes(c, quantity);
+  if (truth && c->err_ref) {  // the truth is the caller's own buffer
+    *ptr = const_cast<double*>(c->err_ref);
+    return 0;
+  }
+  if (truth ? !ec.truth_valid : !ec.valid) {
+    ErrorsRequest r;
+    std::memset(&r, 0, sizeof r);
+    r.mean = (const double*)c->f[source ? ODEF_F_SMOOTH_MEAN : ODEF_F_MEAN].ptr;
+    r.cov = (const double*)c->f[source ? ODEF_F_SMOOTH_COV_TRIL : ODEF_F_COV_TRIL].ptr;
+    r.N = c->cfg.n_traj;
+    r.n_save = c->n_save;
+    r.d = c->d;
+    r.D = c->D;
+    r.TRI = c->TRI;
+    r.ref = c->err_ref;
+    r.field = c->field->errors;
+    r.u0 = c->d_u0;
+    r.p = c->d_p;
+    r.p_shared = c->cfg.params_shared;
+    if (c->adaptive) {
+      r.tsave = (const double*)c->f[ODEF_F_T].ptr;
+      r.nsaved = (const int*)c->f[ODEF_F_NSAVED].ptr;
+      r.t = r.tsave;
+      r.t_sk = r.N;
+      r.t_si = 1;
+      if (!r.tsave || !r.nsaved) return fail(c, "%s: the records of source %d hold no data", who, source);
+    } else {  // the shared grid; final-save mode keeps the one record of the last time
+      r.t = c->d_tgrid + (c->n_save == 1 ? (long)c->tgrid.size() - 1 : 0);
+      r.t_sk = 1;
+      r.t_si = 0;
+    }
+    if (!r.mean || !r.cov) return fail(c, "%s: the records of source %d hold no data", who, source);
+    std::string err;
+    const int rc = truth ? errors_truth(ec, r, c->stream, err)
+                         : errors_run(c->errors, ec, r, c->stream, &c->ms[3], &c->nl[3], c->kname[3], sizeof c->kname[3], err);
+    if (rc) return fail(c, "%s: %s", who, err.c_str());
+  }
+  *ptr = truth ? (void*)ec.truth : quantity == ODEF_E_NUSED - ODEF_E_BASE ? (void*)ec.nused : (void*)ec.val[quantity];
   return 0;
 }
 
@@ -516,6 +600,7 @@ void odef_destroy(odef_ctx* c) {
   if (c->d_tq) (void)hipFree(c->d_tq);
   if (c->d_tab_idx) (void)hipFree(c->d_tab_idx);
   summary_free(c->summary);
+  errors_free(c->errors);
   for (int k = 0; k < 4; ++k)
     if (c->ev[k]) (void)hipEventDestroy(c->ev[k]);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1010,6 +1095,11 @@ int odef_field_bytes(const odef_ctx* c, int field, size_t* bytes) {
     *bytes = summary_bytes(c, (field - ODEF_S_BASE) % 8, n_t);
     return 0;
   }
+  if (c && bytes && is_errors_field(field)) {
+    if (errors_check(c, (field - ODEF_E_BASE) / 8, "odef_field_bytes")) return -1;
+    *bytes = errors_bytes(c, (field - ODEF_E_BASE) % 8);
+    return 0;
+  }
   if (!c || !bytes || field < 0 || field >= ODEF_F_COUNT_) return -1;
   if (field == ODEF_F_T && !c->adaptive) { *bytes = c->tgrid.size() ? (size_t)c->n_save * sizeof(double) : 0; return 0; }
   *bytes = c->f[field].valid;
@@ -1022,6 +1112,15 @@ int odef_get(odef_ctx* c, int field, void* host_dst, size_t bytes) {
     void* src = nullptr;
     size_t have = 0;
     if (summary_field(c, field, "odef_get", &src, &have)) return -1;
+    if (bytes != have) return fail(c, "odef_get: field %d holds %zu bytes, caller asked for %zu", field, have, bytes);
+    HIPCHK(c, hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
+  }
+  if (is_errors_field(field)) {
+    void* src = nullptr;
+    size_t have = 0;
+    if (errors_field(c, field, "odef_get", &src, &have)) return -1;
     if (bytes != have) return fail(c, "odef_get: field %d holds %zu bytes, caller asked for %zu", field, have, bytes);
     HIPCHK(c, hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1048,6 +1147,7 @@ int odef_get(odef_ctx* c, int field, void* host_dst, size_t bytes) {
 int odef_get_device(odef_ctx* c, int field, void** dev_ptr, size_t* bytes) {
   if (!c || !dev_ptr || !bytes) return fail(c, "odef_get_device: null argument");
   if (is_summary_field(field)) return summary_field(c, field, "odef_get_device", dev_ptr, bytes);
+  if (is_errors_field(field)) return errors_field(c, field, "odef_get_device", dev_ptr, bytes);
   if (field < 0 || field >= ODEF_F_COUNT_) return fail(c, "odef_get_device: unknown field %d", field);
   const Buf& b = c->f[field];
   if (!b.ptr || !b.valid) return fail(c, "odef_get_device: field %d holds no data yet", field);
@@ -1058,6 +1158,12 @@ int odef_get_device(odef_ctx* c, int field, void** dev_ptr, size_t* bytes) {
 
 int odef_bind_device(odef_ctx* c, int field, void* dev_ptr, size_t bytes) {
   if (!c) return -1;
+  if (field == ODEF_E_REFERENCE) {  // the truth of the solution errors: caller memory, read only; NULL lets it go
+    c->err_ref = (const double*)dev_ptr;
+    c->err_ref_bytes = dev_ptr ? bytes : 0;
+    for (int k = 0; k < 2; ++k) c->errors.src[k].valid = false;
+    return 0;
+  }
   if (field < 0 || field >= ODEF_F_COUNT_ || field == ODEF_F_U0) return fail(c, "odef_bind_device: field %d cannot be bound", field);
   if (field == ODEF_F_LINEARIZE_AT && dev_ptr && c->cfg.alg != ODEF_IEKS)
     return fail(c, "odef_bind_device: ODEF_F_LINEARIZE_AT belongs to an IEKS context (alg = ODEF_IEKS)");
@@ -1085,13 +1191,13 @@ int odef_synchronize(odef_ctx* c) {
 }
 
 int odef_kernel_name(odef_ctx* c, int which, char* buf, size_t n) {
-  if (!c || which < 0 || which > 2 || !buf || n == 0) return -1;
+  if (!c || which < 0 || which > 3 || !buf || n == 0) return -1;
   std::snprintf(buf, n, "%s", c->kname[which]);
   return 0;
 }
 
 int odef_kernel_time_ms(odef_ctx* c, int which, float* ms, int* n_launches) {
-  if (!c || which < 0 || which > 2 || !ms) return -1;
+  if (!c || which < 0 || which > 3 || !ms) return -1;
   *ms = c->ms[which];
   if (n_launches) *n_launches = c->nl[which];
   return 0;

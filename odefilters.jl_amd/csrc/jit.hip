@@ -82,6 +82,7 @@ std::string module_source(const JitRhs& r, int q, int ek1, int mv, int ieks) {
   std::string s;
   if (D > 12 && !team) s += "#define ODEF_ROWSTORE_FREE_OFFSET 1\n";  // see RowStore (ek_lane.h)
   s += team ? "#include \"team_launch_impl.h\"\n" : "#include \"ek_kernels.h\"\n";
+  s += "#include \"errors_field.h\"\n";  // the solution-error kernels, when the struct has an `analytic`
   s += "namespace odef {\n";
   s += r.source;
   s += "\nstruct RhsJit : " + r.name + " { static constexpr const char* name = \"" + r.name + "\"; };\n";
@@ -95,12 +96,12 @@ std::string module_source(const JitRhs& r, int q, int ek1, int mv, int ieks) {
          ">, team_sample<" + TT + ">, team_smooth_ws<" + TT + ">";
   else
     s += "lane_filter<RhsJit, " + Q + ", " + EK + ", " + MV + ", " + (ieks ? "true" : "false") + ">, lane_smooth<" + T + ">, nullptr, lane_dense<" + T + ">, lane_sample<" + T + ">, nullptr";
-  s += "};\n  return &t;\n}\n";
+  s += ", errors_launcher<RhsJit>()};\n  return &t;\n}\n";
   return s;
 }
 
 // What odef_rhs_compile builds for d > 10 (no lane kernel exists to try the text on): the vector field in double, in
-// forward mode (the Jacobian EK1 needs when the struct has none) and on Taylor jets (the initialisation)
+// forward mode (the Jacobian EK1 needs when the struct has none), on Taylor jets (the initialisation), and its `analytic` if it has one
 std::string probe_translation_unit(const JitRhs& r) {
   const std::string DD = std::to_string(r.d);
   std::string s = "#include \"ek_lane.h\"\nnamespace odef {\n";
@@ -108,6 +109,8 @@ std::string probe_translation_unit(const JitRhs& r) {
   s += "\nusing RhsJit = " + r.name + ";\n";
   s += "static_assert(RhsJit::d == " + DD + ", \"d of the struct differs from the d passed to odef_rhs_compile\");\n";
   s += "static_assert(RhsJit::np == " + std::to_string(r.np) + ", \"np of the struct differs from the n_params passed to odef_rhs_compile\");\n";
+  s += "template <class R>\n__device__ void probe_analytic(const double (&u0)[R::d], const double* p, double t, double& acc) {\n"
+       "  if constexpr (HasAnalytic<R>::value) {\n    double ua[R::d];\n    R::analytic(u0, p, t, ua);\n    acc += ua[0];\n  }\n}\n";
   s += "extern \"C\" __global__ void odef_jit_probe(const double* u, const double* p, double* out) {\n"
        "  constexpr int d = " + DD + ";\n"
        "  double uu[d], du[d], J[d][d], m0[2 * d];\n"
@@ -116,6 +119,7 @@ std::string probe_translation_unit(const JitRhs& r) {
        "  rhs_jacobian<RhsJit>(uu, p, J);\n"
        "  taylor_init<RhsJit, 1>(uu, p, m0);\n"
        "  double acc = 0.0;\n"
+       "  probe_analytic<RhsJit>(uu, p, u[0], acc);\n"
        "  for (int a = 0; a < d; ++a) acc += du[a] + J[a][a] + m0[d + a];\n"
        "  out[0] = acc;\n}\n";
   s += "}  // namespace odef\n";

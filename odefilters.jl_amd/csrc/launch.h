@@ -8,6 +8,8 @@
 #include "rows_launch.h"
 
 namespace odef {
+struct ErrArgs;       // errors_kernels.h
+struct AnalyticArgs;  // errors_kernels.h
 // The launchers say which kernel they picked (printf-style; the name a profiler prints); api.hip hands it out through
 // odef_kernel_name.  One slot per host thread: read back right after the launch call.
 void note_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
@@ -29,6 +31,9 @@ struct FieldLaunch {
   size_t (*smooth_ws)(int q);  // doubles of workspace per trajectory (smoother) / per grid slot (dense output, sampling)
   // smooth_staged and smooth_ws are null for the lane / row-team fields (their launchers ignore `ws` and the stage): a table
   // with them is a field on the workgroup-per-trajectory kernels
+  // solution errors against the field's own `analytic` (errors_field.h); null for a field that has none
+  int (*errors)(const ErrArgs& a, const AnalyticArgs& t, unsigned grid, unsigned block, size_t lds, double* truth_out, hipStream_t s,
+                char* kname, size_t kname_n) = nullptr;
 };
 // Layout stamp of what crosses between the library and a run-time compiled module (jit.hip builds one from the headers it
 // finds at run time: a tree whose headers moved on without a rebuild of the library must be refused, not launched)

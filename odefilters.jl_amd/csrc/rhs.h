@@ -191,6 +191,13 @@ struct HasJac { static constexpr bool value = false; };
 template <class RHS>
 struct HasJac<RHS, odef_void_t<decltype(&RHS::jac)>> { static constexpr bool value = true; };
 
+// Optional: `analytic(u0, p, t, out)`, the closed-form solution at the absolute time t (DiffEqBase's `f.analytic(u0, p, t)`), written
+// once in the scalar type like `f`.  A field that has one gets solution errors on the device (errors_field.h).
+template <class RHS, class = void>
+struct HasAnalytic { static constexpr bool value = false; };
+template <class RHS>
+struct HasAnalytic<RHS, odef_void_t<decltype(&RHS::template analytic<double>)>> { static constexpr bool value = true; };
+
 // J = df/du at u: the vector field's own `jac` when it has one, forward-mode differentiation of `f` otherwise
 template <class RHS>
 __device__ inline void rhs_jacobian(const double (&u)[RHS::d], const double* p, double (&J)[RHS::d][RHS::d]) {
@@ -311,6 +318,12 @@ struct RhsLinear {  // test/convergence.jl:9-14, test/state_init.jl:12-17
     J[0][1] = 0.0;
     J[1][0] = 0.0;
     J[1][1] = p[1];
+  }
+  // u(t) = u0 exp(p t), the reference's `analytic = (u0, p, t) -> u0 .* exp(p t)` (test/convergence.jl:13): t0 = 0
+  template <class T>
+  __device__ static void analytic(const T (&u0)[2], const double* p, T t, T (&out)[2]) {
+    out[0] = u0[0] * exp(p[0] * t);
+    out[1] = u0[1] * exp(p[1] * t);
   }
 };
 

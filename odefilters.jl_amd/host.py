@@ -58,6 +58,33 @@ def summary_field(source: int, quantity: int) -> int:
 
 def _is_summary_field(f: int) -> bool:
     return S_BASE <= f < S_BASE + 24 and (f - S_BASE) % 8 < 4
+
+
+# solution errors per trajectory (odef_errors_field, include/odefilter.h): id = E_BASE + 8 * source + quantity
+E_BASE = 128
+E_SOURCE_FILTER, E_SOURCE_SMOOTH = 0, 1
+E_FINAL, E_L2, E_LINF, E_CHI2, E_NUSED, E_U_ANALYTIC = range(6)
+E_REFERENCE = 144  # odef_bind_device only: the truth [n_save][d][N] in device memory
+ERRORS_FIELDS = {
+    "ODEF_E_BASE": 128,
+    "ODEF_E_FINAL": 128, "ODEF_E_L2": 129, "ODEF_E_LINF": 130, "ODEF_E_CHI2": 131, "ODEF_E_NUSED": 132, "ODEF_E_U_ANALYTIC": 133,
+    "ODEF_E_SMOOTH_FINAL": 136, "ODEF_E_SMOOTH_L2": 137, "ODEF_E_SMOOTH_LINF": 138, "ODEF_E_SMOOTH_CHI2": 139,
+    "ODEF_E_SMOOTH_NUSED": 140, "ODEF_E_SMOOTH_U_ANALYTIC": 141,
+    "ODEF_E_REFERENCE": 144,
+}
+_NO_TRUTH = "nothing to compare with"  # the library's refusal for a field without `analytic` and no bound reference
+
+
+def errors_field(source: int, quantity: int) -> int:
+    """Field id of a solution-error array: source 0 filter / 1 smoothed records, quantity 0 FINAL / 1 L2 / 2 LINF / 3 CHI2 /
+    4 NUSED / 5 U_ANALYTIC."""
+    if source not in (0, 1) or quantity not in range(6):
+        raise OdefError(f"no solution-error field for source {source}, quantity {quantity}")
+    return E_BASE + 8 * source + quantity
+
+
+def _is_errors_field(f: int) -> bool:
+    return E_BASE <= f < E_BASE + 16 and (f - E_BASE) % 8 < 6
 MAX_ORDER = 5
 
 
@@ -272,6 +299,12 @@ class DeviceGroup:
             parts.append(out)
         return np.concatenate(parts, axis=-1)
 
+    def solution_errors(self, source: int):
+        """Solution errors of the WHOLE ensemble (`odef_errors_field`): every shard runs the pass on its own device, the
+        per-trajectory arrays are joined along the trajectory axis.  dict with "l∞", "l2", "final", "chi2" [N] and "nused"."""
+        parts = [Context._solution_errors(self.lib, self.lib.odef_group_ctx(self._h, g), source) for g in range(self.G)]
+        return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
     def ensemble_moments(self, source: int):
         """Ensemble summary of the WHOLE ensemble: every shard reduces its own records on its device (`odef_summary_field`),
         the per-shard blocks (kilobytes) are pooled on the host with `merge_moments`.  Returns (count, mean, within, between)."""
@@ -464,12 +497,16 @@ class Context:
         dt = np.int32 if f in _INT_FIELDS else np.float64
         if _is_summary_field(f):  # [n_t] int64 counts, [n_t, d] means, [n_t, d(d+1)/2] packed covariances
             dt = np.int64 if (f - S_BASE) % 8 == S_COUNT else np.float64
+        if _is_errors_field(f):  # [N] per trajectory (NUSED int64), U_ANALYTIC [n_save, d, N]
+            dt = np.int64 if (f - E_BASE) % 8 == E_NUSED else np.float64
         out = np.empty(nbytes // np.dtype(dt).itemsize, dtype=dt)
         self._chk(self.lib.odef_get(self._h, f, out.ctypes.data_as(_vp), nbytes))
         if _is_summary_field(f):
             qty = (f - S_BASE) % 8
             return out if qty == S_COUNT else out.reshape(-1, self.d if qty == S_MEAN else self.d * (self.d + 1) // 2)
         ns, N = self.n_save, self.N
+        if _is_errors_field(f):
+            return out.reshape(ns, self.d, N) if (f - E_BASE) % 8 == E_U_ANALYTIC else out
         if f in (F_MEAN, F_SMOOTH_MEAN):
             return out.reshape(ns, self.D, N)
         if f in (F_COV_TRIL, F_SMOOTH_COV_TRIL):
@@ -490,6 +527,30 @@ class Context:
         lower triangles.  The first request after the records changed launches the reduction; later ones read the cache."""
         return tuple(self.get(summary_field(source, qty)) for qty in range(4))
 
+    @staticmethod
+    def _solution_errors(lib, h, source: int):
+        out = {}
+        for key, qty in (("l∞", E_LINF), ("l2", E_L2), ("final", E_FINAL), ("chi2", E_CHI2), ("nused", E_NUSED)):
+            f, b = errors_field(source, qty), C.c_size_t()
+            if lib.odef_field_bytes(h, f, C.byref(b)) != 0:
+                raise OdefError(lib.odef_last_error(h).decode())
+            a = np.empty(b.value // 8, dtype=np.int64 if qty == E_NUSED else np.float64)
+            if lib.odef_get(h, f, a.ctypes.data_as(_vp), b.value) != 0:
+                raise OdefError(lib.odef_last_error(h).decode())
+            out[key] = a
+        return out
+
+    def solution_errors(self, source: int):
+        """Per-trajectory errors of the filter (0) or smoothed (1) solution against the truth -- the vector field's `analytic`, or
+        a reference bound with `bind_reference` --, reduced on the device (`odef_errors_field`): dict with "l∞", "l2", "final"
+        (DiffEqBase's sol.errors), "chi2" (mean_k e' Sigma^+ e / d, ~ 1 for a calibrated posterior), each [N], and "nused"."""
+        return self._solution_errors(self.lib, self._h, source)
+
+    def bind_reference(self, ptr: int, nbytes: int):
+        """The truth of `solution_errors` for a field without a closed form (`appxtrue`): [n_save][d][N] doubles in device memory,
+        read only -- e.g. a tight solve's `odef_dense_output` on this grid.  Fixed grids only; ptr = 0 lets it go."""
+        self._chk(self.lib.odef_bind_device(self._h, E_REFERENCE, _vp(ptr) if ptr else None, nbytes))
+
     def device_ptr(self, f: int):
         p, b = _vp(), C.c_size_t()
         self._chk(self.lib.odef_get_device(self._h, f, C.byref(p), C.byref(b)))
@@ -499,7 +560,8 @@ class Context:
         self._chk(self.lib.odef_bind_device(self._h, f, _vp(ptr), nbytes))
 
     def kernel_name(self, which=0) -> str:
-        """Name of the kernel the last filter (0) / smoother (1) / ensemble-summary (2) pass launched, as a profiler prints it."""
+        """Name of the kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) pass launched, as a
+        profiler prints it."""
         buf = C.create_string_buffer(256)
         self._chk(self.lib.odef_kernel_name(self._h, which, buf, 256))
         return buf.value.decode()
@@ -904,6 +966,37 @@ class EnsembleSolution:
         sm = self.smoothed if smoothed is None else smoothed
         m, c = self.ctx.dense_output(tq, sm)
         return m.transpose(2, 0, 1), unpack_tril(c.transpose(2, 0, 1), self.D)
+
+    @property
+    def errors(self):
+        """sol.errors (src/solution.jl:11, 68-74): dict with "l∞", "l2", "final" -- DiffEqBase's timeseries errors of sol.u (the
+        smoothed means when the solution is smoothed) against the truth -- plus "chi2", each [N], computed on the device.  None
+        when the vector field has no `analytic` and no reference is bound, as the reference returns `nothing`."""
+        if "errors" not in self._cache:
+            try:
+                e = self.ctx.solution_errors(E_SOURCE_SMOOTH if self.smoothed else E_SOURCE_FILTER)
+                e.pop("nused")
+            except OdefError as ex:
+                if _NO_TRUTH not in str(ex):
+                    raise
+                e = None
+            self._cache["errors"] = e
+        return self._cache["errors"]
+
+    @property
+    def u_analytic(self):
+        """sol.u_analytic (src/solution.jl:10): the truth at every trajectory's own save times, [N, n_save, d] like `u`; None
+        without a truth."""
+        if "u_analytic" not in self._cache:
+            try:
+                a = self.ctx.get(errors_field(E_SOURCE_SMOOTH if self.smoothed else E_SOURCE_FILTER, E_U_ANALYTIC))
+                a = self._compact(a.transpose(2, 0, 1))
+            except OdefError as ex:
+                if _NO_TRUTH not in str(ex):
+                    raise
+                a = None
+            self._cache["u_analytic"] = a
+        return self._cache["u_analytic"]
 
     def summary(self, t=None, smoothed: Optional[bool] = None) -> EnsembleSummary:
         """Mean path of the ensemble and its uncertainty, reduced on the device (`odef_summary_field`): nothing but the four

@@ -30,3 +30,5 @@ PY
 LD_PRELOAD=$(g++ -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 python /tmp/odef_san_run.py
 # the ensemble-summary reduction (tests/emul/emul_summary.cpp), every case of its emulation test
 ODEF_EMUL_SANITIZE=1 LD_PRELOAD=$(g++ -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 python -m pytest tests/test_summary_emul.py -q -p no:cacheprovider
+# the solution-error kernels (tests/emul/emul_errors.cpp), every case of their emulation test
+ODEF_EMUL_SANITIZE=1 LD_PRELOAD=$(g++ -print-file-name=libasan.so) ASAN_OPTIONS=detect_leaks=0 python -m pytest tests/test_errors_emul.py -q -p no:cacheprovider
