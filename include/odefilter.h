@@ -107,7 +107,8 @@ typedef enum {
   ODEF_RHS_VANDERPOL = 3,      /* u' = (u2, mu((1-u1^2)u2 - u1)), p = (mu) */
   ODEF_RHS_LINEAR = 4,         /* u_i' = p_i u_i, d = 2 */
   ODEF_RHS_PLEIADES = 5,       /* 7-body, d = 28, no parameters; workgroup-per-trajectory kernels (matrix cores) */
-  ODEF_RHS_LORENZ96 = 6        /* u_i' = (u_{i+1} - u_{i-2}) u_{i-1} - u_i + F, d = 16, p = (F); workgroup-per-trajectory kernels */
+  ODEF_RHS_LORENZ96 = 6,       /* u_i' = (u_{i+1} - u_{i-2}) u_{i-1} - u_i + F, d = 16, p = (F); workgroup-per-trajectory kernels */
+  ODEF_RHS_FORCED = 7          /* time-dependent: u' = (p0 u1 + p1 t, p2 t u2), d = 2, p = (p0, p1, p2); has an `analytic` */
 } odef_rhs;
 typedef enum { ODEF_SAVE_FINAL = 0, ODEF_SAVE_EVERYSTEP = 1 } odef_save_mode;
 typedef enum {
@@ -257,6 +258,19 @@ const char* odef_last_error(const odef_ctx* ctx); /* ctx may be NULL: last error
  *       template <class T>   // optional: the closed-form solution at the absolute time t (f.analytic); with it the
  *       __device__ static void analytic(const T (&u0)[3], const double* p, T t, T (&out)[3]) { ... }  // odef_errors_field ids work
  *     };
+ *
+ * A TIME-DEPENDENT field f(u, p, t) (the reference evaluates f and f.jac at the step's new time, src/perform_step.jl:106,117)
+ * opts in with `static constexpr bool has_time = true;` and takes the absolute time behind p, in the scalar type of u:
+ *
+ *       template <class T> __device__ static void f(const T (&u)[3], const double* p, T t, T (&du)[3]) { ... }
+ *       __device__ static void jac(const double (&u)[3], const double* p, double t, double (&J)[3][3]) { ... }  // optional
+ *       template <class T> __device__ static void analytic(const T (&u0)[3], const double* p, T t0, T t, T (&out)[3]) { ... }
+ *           // optional; (any field's analytic may take the initial time t0 in front of t like this)
+ *
+ * The step evaluates f and the Jacobian at its new time (fixed grids: the grid point; adaptive: t + dt of the attempt), and the
+ * Taylor initialisation differentiates in t as well (u'' = f_u f + f_t, ...).  Such a field runs on the lane and row-team kernels
+ * (d(q+1) <= 20, d <= 10); odef_create refuses it above, where the workgroup-per-trajectory kernels would be needed.  Setting
+ * has_time with the three-argument f is a compile error.
  *
  * A hipcc child process ($ODEFILTER_HIP_HIPCC, else hipcc on PATH, else /opt/rocm/bin/hipcc) compiles the library's
  * own kernels around it for gfx950 (include_dir = directory holding the csrc headers; NULL: $ODEFILTER_HIP_INCLUDE, else

@@ -20,7 +20,8 @@ struct OdefConfig                      # odef_config, 56 bytes
     device::Int32; want_loglik::Int32; n_traj::Int64
 end
 
-const RHS_IDS = Dict(:fhn => 0, :lorenz63 => 1, :lotka_volterra => 2, :vanderpol => 3, :linear => 4, :pleiades => 5, :lorenz96 => 6)
+const RHS_IDS = Dict(:fhn => 0, :lorenz63 => 1, :lotka_volterra => 2, :vanderpol => 3, :linear => 4, :pleiades => 5, :lorenz96 => 6,
+                     :forced => 7)  # :forced is time-dependent, f(u, p, t)
 # src/caches.jl:89-96; the MV models (diagonal diffusion, EK0 only, the lane kernels: d(q+1) <= 20) keep d diffusions per save
 const DIFFUSIONS = Dict(:dynamic => 0, :fixed => 1, :fixedMAP => 2, :dynamicMV => 3, :fixedMV => 4)
 const MV_DIFFUSIONS = (:dynamicMV, :fixedMV)

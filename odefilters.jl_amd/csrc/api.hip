@@ -35,7 +35,7 @@ struct Buf {
 };
 
 struct RhsInfo { int d, np; };
-const RhsInfo kRhs[] = {{2, 3}, {3, 3}, {2, 4}, {2, 1}, {2, 2}, {28, 0}, {16, 1}};
+const RhsInfo kRhs[] = {{2, 3}, {3, 3}, {2, 4}, {2, 1}, {2, 2}, {28, 0}, {16, 1}, {2, 3}};
 
 }  // namespace
 
@@ -505,7 +505,7 @@ int odef_create(odef_ctx** out, const odef_config* cfg) {
   if (cfg->rhs_id >= kJitFirstId) {
     if (!jit_lookup(cfg->rhs_id, &ri.d, &ri.np)) return fail(nullptr, "odef_create: unknown run-time rhs_id %d", cfg->rhs_id);
   } else {
-    if (cfg->rhs_id < 0 || cfg->rhs_id > ODEF_RHS_LORENZ96) return fail(nullptr, "odef_create: unknown rhs_id %d", cfg->rhs_id);
+    if (cfg->rhs_id < 0 || cfg->rhs_id > ODEF_RHS_FORCED) return fail(nullptr, "odef_create: unknown rhs_id %d", cfg->rhs_id);
     ri = kRhs[cfg->rhs_id];
   }
   if (cfg->d != ri.d) return fail(nullptr, "odef_create: rhs %d has dimension %d, got d=%d", cfg->rhs_id, ri.d, cfg->d);
@@ -537,6 +537,11 @@ int odef_create(odef_ctx** out, const odef_config* cfg) {
                   cfg->d * (cfg->order + 1));
   }
   if (cfg->n_traj <= 0) return fail(nullptr, "odef_create: n_traj must be positive");
+  // a time-dependent run-time field (has_time, csrc/rhs.h): the workgroup-per-trajectory kernels carry no time
+  if (cfg->rhs_id >= kJitFirstId && jit_has_time(cfg->rhs_id) && jit_team_path(cfg->d, cfg->order))
+    return fail(nullptr, "odef_create: time-dependent fields run on the lane and row-team kernels (state dimension d(q+1) <= 20, d <= 10); "
+                         "rhs %d with d = %d, d(q+1) = %d would need the workgroup-per-trajectory kernels", cfg->rhs_id, cfg->d,
+                cfg->d * (cfg->order + 1));
   // run-time compiled fields: lane / row-team kernels up to state dimension 20 (d <= 10), the workgroup-per-trajectory kernels above
   if (cfg->rhs_id >= kJitFirstId && jit_team_path(cfg->d, cfg->order) && (cfg->d % 2 != 0 || cfg->d > 32 || cfg->d * (cfg->order + 1) > 176))
     return fail(nullptr, "odef_create: run-time compiled vector fields above state dimension 20 run on the workgroup-per-trajectory kernels: even d <= 32 and d(q+1) <= 176 (got d = %d, d(q+1) = %d)",
@@ -846,6 +851,7 @@ int odef_solve_fixed(odef_ctx* c, const double* tgrid, int64_t n_t) {
   P.nsteps = nsteps;
   P.t0 = c->t0;
   P.lin = lin;
+  P.tgrid = c->d_tgrid;
   size_t have = 0;
   if (team_path(c)) {
     if (P.everystep) {  // the matrix-core kernel writes its records through the trajectory-major stage when all of them fit
@@ -1565,6 +1571,7 @@ const FieldLaunch* field_launch(int rhs_id) {
     case ODEF_RHS_LOTKA_VOLTERRA: return field_lotka_volterra();
     case ODEF_RHS_VANDERPOL: return field_vanderpol();
     case ODEF_RHS_LINEAR: return field_linear();
+    case ODEF_RHS_FORCED: return field_forced();
     case ODEF_RHS_PLEIADES: return field_pleiades();
     case ODEF_RHS_LORENZ96: return field_lorenz96();
     default: return nullptr;

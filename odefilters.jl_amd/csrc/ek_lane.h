@@ -50,6 +50,9 @@ struct FilterParams {
   // IEKS (ODEF_IEKS, fixed grid, every step saved): the linearisation points [n_t][d][N] -- the u part of the previous
   // iterate's smoothed mean, step s -> s + 1 reads row s + 1 (src/perform_step.jl:111-125); null: the step is EK1
   const double* lin;
+  // time-dependent fields (HasTime, rhs.h), fixed grid: the grid itself, [nsteps + 1]; step n -> n + 1 evaluates f and the
+  // Jacobian at tgrid[n + 1] (src/perform_step.jl:106,117).  Read by the kernels of such fields only.
+  const double* tgrid;
 };
 
 // Row store: `base` is a wave-uniform pointer to element [field row 0][first trajectory of the
@@ -211,6 +214,7 @@ __device__ inline bool all_finite(const double (&m)[D]) {
 // LAG (with EVERY): the record of step n is stored while step n + 1 runs (LaggedSink) -- for small ensembles.
 // MV: the diagonal diffusion models (EKStep), d diffusions per record.
 // IEKS: the Jacobian of every step at P.lin (EKStep), EK1 and every step saved only.
+// A time-dependent field (HasTime<RHS>): the initialisation at P.t0, step n -> n + 1 at P.tgrid[n + 1].
 template <class RHS, int q, bool IS_EK1, bool EVERY, bool LAG = false, bool MV = false, bool IEKS = false>
 __device__ inline void filter_fixed_lane(const FilterParams& P, long i0, unsigned lane) {
   static_assert(!IEKS || (IS_EK1 && EVERY && !MV), "IEKS: EK1, every step saved, scalar diffusion models");
@@ -225,7 +229,8 @@ __device__ inline void filter_fixed_lane(const FilterParams& P, long i0, unsigne
   for (int a = 0; a < d; ++a) u0[a] = P.u0[(size_t)a * P.N + i];
 
   double m[D], C[TRI];
-  taylor_init<RHS, q>(u0, pl, m);
+  if constexpr (HasTime<RHS>::value) taylor_init<RHS, q>(u0, pl, m, P.t0);
+  else taylor_init<RHS, q>(u0, pl, m);
 #pragma unroll
   for (int k = 0; k < TRI; ++k) C[k] = 0.0;
   using Diff = SigT<d, MV>;
@@ -241,8 +246,9 @@ __device__ inline void filter_fixed_lane(const FilterParams& P, long i0, unsigne
   for (long n = 0; n < P.nsteps; ++n) {
     const GlobalTab tab{P.ptab + (size_t)uniform_load(P.tab_idx + n) * kTabStride};  // wave-uniform, scalar loads
     double m2[D], C2[TRI], es[d];
-    std::conditional_t<MV, StepAuxMV<d>, std::conditional_t<IEKS, StepAuxLin<d>, StepAux>> aux;
+    StepAuxFor<RHS, std::conditional_t<MV, StepAuxMV<d>, std::conditional_t<IEKS, StepAuxLin<d>, StepAux>>> aux;
     aux.chol_fix = 0;
+    if constexpr (HasTime<RHS>::value) aux.tnew = uniform_load(P.tgrid + n + 1);  // wave-uniform, a scalar load
     const size_t Nn = (size_t)P.N;
     if constexpr (IEKS) {  // this step's linearisation point, loaded first so that its latency hides behind the predict
 #pragma unroll
@@ -350,7 +356,8 @@ __device__ inline void filter_adaptive_lane(const FilterParams& P, long i0, unsi
   for (int a = 0; a < d; ++a) u0[a] = P.u0[(size_t)a * P.N + i];
 
   double m[D], C[TRI];
-  taylor_init<RHS, q>(u0, pl, m);
+  if constexpr (HasTime<RHS>::value) taylor_init<RHS, q>(u0, pl, m, P.t0);
+  else taylor_init<RHS, q>(u0, pl, m);
 #pragma unroll
   for (int k = 0; k < TRI; ++k) C[k] = 0.0;
   SigT<d, MV> gdiff{};
@@ -378,8 +385,9 @@ __device__ inline void filter_adaptive_lane(const FilterParams& P, long i0, unsi
     precond_table_fast<q, NB, true>(h, tabv);  // no division, no libm pow: rebuilt at every attempted step
     const LocalTab tab{tabv};
     double es[d];
-    std::conditional_t<MV, StepAuxMV<d>, StepAux> aux;
+    StepAuxFor<RHS, std::conditional_t<MV, StepAuxMV<d>, StepAux>> aux;
     aux.chol_fix = 0;
+    if constexpr (HasTime<RHS>::value) aux.tnew = t + h;  // this attempt's new time: what T receives when it is accepted
     {
       double m2[D], C2[TRI];
       NoSink nosink;

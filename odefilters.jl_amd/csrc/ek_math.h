@@ -425,11 +425,27 @@ struct StepAuxLin : StepAux {
   double u_lin[d];
 };
 
+// ... and of a step of a time-dependent field (HasTime, rhs.h), on top of any of the three: the step's new time, at which f and the
+// Jacobian are evaluated (src/perform_step.jl:106,117; set by the caller before run)
+template <class Base>
+struct StepAuxTime : Base {
+  double tnew;
+};
+template <class RHS, class Base>
+using StepAuxFor = std::conditional_t<HasTime<RHS>::value, StepAuxTime<Base>, Base>;
+// the time of the step an `aux` record belongs to; an autonomous field's record carries none
+template <class RHS, class Aux>
+__device__ inline double step_time(const Aux& aux) {
+  if constexpr (HasTime<RHS>::value) return aux.tnew;
+  else return 0.0;
+}
+
 // MV: the diagonal diffusion models (EK0 only, src/diffusions.jl:96, :125); `fixed_diffusion` is then the C ABI's
 // odef_diffusion value 3 (:dynamicMV) or 4 (:fixedMV), `prev_global` a SigV<d> and `aux` a StepAuxMV<d>.
 // IEKS: the iterated extended Kalman smoother's step (src/perform_step.jl:111-125): `aux` is a StepAuxLin<d> whose `u_lin` holds
 // the linearisation point (the previous iterate's smoothed u at the new time), the Jacobian is evaluated there; f stays at the
 // prediction.
+// A time-dependent field (HasTime<RHS>): `aux` is a StepAuxTime<...> of the above, f and the Jacobian are evaluated at `aux.tnew`.
 template <class RHS, int q, bool IS_EK1, bool MV = false, bool IEKS = false>
 struct EKStep {
   static_assert(!(MV && IS_EK1), "MV diffusion models require EK0");
@@ -490,7 +506,8 @@ struct EKStep {
 #pragma unroll
     for (int a = 0; a < d; ++a) up[a] = pi0 * mp[a];
     sink.tick();
-    RHS::f(up, p, du);
+    if constexpr (HasTime<RHS>::value) rhs_eval<RHS>(up, p, aux.tnew, du);
+    else RHS::f(up, p, du);
 #pragma unroll
     for (int a = 0; a < d; ++a) z[a] = pi1 * mp[d + a] - du[a];
     sink.tick();
@@ -499,8 +516,8 @@ struct EKStep {
     if constexpr (IS_EK1) {
       double Jm[d][d];
       // f.jac, else forward-mode AD (src/perform_step.jl:116-121); IEKS: at linearize_at(t).mu (:111-113)
-      if constexpr (IEKS) rhs_jacobian<RHS>(aux.u_lin, p, Jm);
-      else rhs_jacobian<RHS>(up, p, Jm);
+      if constexpr (IEKS) rhs_jacobian<RHS>(aux.u_lin, p, step_time<RHS>(aux), Jm);
+      else rhs_jacobian<RHS>(up, p, step_time<RHS>(aux), Jm);
 #pragma unroll
       for (int r = 0; r < d; ++r)
 #pragma unroll
@@ -780,9 +797,11 @@ struct NoSink {
 
 // Taylor-mode initialisation (src/state_initialization.jl:2-53): m0 = [u0; u'(t0); ...; u^(q)(t0)],
 // Sigma0 = 0 (the q+1 exact `condition_on!` calls leave a zero covariance, test/solution.jl:38-41).
+// A time-dependent field is handed t as the jet {t0, 1, 0, ...}: the recursion then yields the TOTAL derivatives
+// (u'' = f_u f + f_t, ...), which the reference leaves out (its assert at src/state_initialization.jl:20-22).
 template <class RHS, int q>
 __device__ inline void taylor_init(const double (&u0)[RHS::d], const double* __restrict__ p,
-                                   double (&m0)[RHS::d * (q + 1)]) {
+                                   double (&m0)[RHS::d * (q + 1)], double t0 = 0.0) {
   constexpr int d = RHS::d, NB = q + 1;
   double coef[d][NB];
 #pragma unroll
@@ -798,7 +817,13 @@ __device__ inline void taylor_init(const double (&u0)[RHS::d], const double* __r
     for (int a = 0; a < d; ++a)
 #pragma unroll
       for (int c = 0; c < NB; ++c) u[a].c[c] = coef[a][c];
-    RHS::f(u, p, fu);
+    if constexpr (HasTime<RHS>::value) {
+      Jet<NB> tj(t0);
+      tj.c[1] = 1.0;
+      RHS::f(u, p, tj, fu);
+    } else {
+      RHS::f(u, p, fu);
+    }
 #pragma unroll
     for (int a = 0; a < d; ++a) coef[a][k + 1] = fu[a].c[k] / (k + 1);
   }

@@ -80,17 +80,31 @@ struct AnalyticArgs {
   long N, t_sk, t_si;
   int p_shared;
 };
+// ... whose solution depends on the initial time: `analytic(u0, p, t0, t, out)`; t0 is the time of save 0
+template <class...>
+using err_void_t = void;
+template <class RHS, class = void>
+struct AnalyticTakesT0 { static constexpr bool value = false; };
+template <class RHS>
+struct AnalyticTakesT0<RHS, err_void_t<decltype(RHS::analytic(*(const double (*)[RHS::d])nullptr, (const double*)nullptr, 0.0, 0.0,
+                                                              *(double (*)[RHS::d])nullptr))>> {
+  static constexpr bool value = true;
+};
 template <class RHS>
 struct TruthAnalytic {
   using Args = AnalyticArgs;
   Args a;
-  double u0l[RHS::d], pl[RHS::np > 0 ? RHS::np : 1], out[RHS::d];
+  double u0l[RHS::d], pl[RHS::np > 0 ? RHS::np : 1], out[RHS::d], t0;
   __device__ explicit TruthAnalytic(const Args& args) : a(args) {}
   __device__ void init(long i) {
     for (int c = 0; c < RHS::d; ++c) u0l[c] = a.u0[(size_t)c * a.N + i];
     for (int c = 0; c < RHS::np; ++c) pl[c] = a.p_shared ? a.p[c] : a.p[(size_t)c * a.N + i];
+    if constexpr (AnalyticTakesT0<RHS>::value) t0 = a.t[i * a.t_si];
   }
-  __device__ void at(long k, long i) { RHS::analytic(u0l, pl, a.t[k * a.t_sk + i * a.t_si], out); }
+  __device__ void at(long k, long i) {
+    if constexpr (AnalyticTakesT0<RHS>::value) RHS::analytic(u0l, pl, t0, a.t[k * a.t_sk + i * a.t_si], out);
+    else RHS::analytic(u0l, pl, a.t[k * a.t_sk + i * a.t_si], out);
+  }
   __device__ double get(int c) const { return out[c]; }
 };
 

@@ -100,6 +100,7 @@ struct TeamFilter {
     if (t.tid == 0) {
       double u_[d], du_[d];
       for (int a = 0; a < d; ++a) u_[a] = up[a];
+      static_assert(!HasTime<RHS>::value, "time-dependent fields run on the lane and row-team kernels (DESIGN.md 3.14)");
       RHS::f(u_, p, du_);
       for (int a = 0; a < d; ++a) du[a] = du_[a];
       if constexpr (IS_EK1) RHS::jac(u_, p, *reinterpret_cast<double (*)[d][d]>(H0));  // raw J, scaled below

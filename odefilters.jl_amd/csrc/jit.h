@@ -12,6 +12,8 @@ inline bool jit_team_path(int d, int q) { return d * (q + 1) > 20 || d > 10; }
 // returns the new rhs id (>= kJitFirstId) or -1 with the compiler log in `err`
 int jit_register(const char* name, const char* source, int d, int np, const char* include_dir, std::string& err);
 bool jit_lookup(int rhs_id, int* d, int* np);
+// whether the field is time-dependent (`has_time` in its struct, rhs.h): such a field runs on the lane and row-team kernels only
+bool jit_has_time(int rhs_id);
 // The launch table (launch.h) of a run-time compiled field for one order and algorithm: compiled once per (rhs, order, alg)
 // into a host + device shared object around the field (seconds; minutes on the workgroup-per-trajectory kernels).
 // abi_stamp: team_abi_stamp() of the library

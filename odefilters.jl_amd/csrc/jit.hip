@@ -36,6 +36,7 @@ namespace {
 struct JitRhs {
   std::string name, source, include_dir;
   int d, np;
+  bool has_time = false;  // f(u, p, t): `static constexpr bool has_time = true` in the struct (rhs.h)
 };
 
 std::mutex g_mu;
@@ -68,6 +69,11 @@ std::string default_include_dir() {
 #endif
 }
 
+// a kernel whose NAME says whether the struct is a time-dependent field (HasTime, rhs.h): jit_register reads it off the code object
+const char* const kTimeFlag =
+    "template <bool HAS_TIME>\n__global__ void odef_jit_time_flag() {}\n"
+    "template __global__ void odef_jit_time_flag<HasTime<RhsJit>::value>();\n";
+
 // The module of one order and algorithm: the launchers of the compiled-in fields instantiated around the user's struct --
 // the lane / row-team ones of ek_kernels.h up to state dimension 20, the workgroup-per-trajectory ones of team_launch_impl.h
 // (kernels: team_kernels.h) above (exactly what inst_lorenz63.hip / inst_lorenz96.hip are for a compiled-in field) -- exporting their table.
@@ -88,6 +94,7 @@ std::string module_source(const JitRhs& r, int q, int ek1, int mv, int ieks) {
   s += "\nstruct RhsJit : " + r.name + " { static constexpr const char* name = \"" + r.name + "\"; };\n";
   s += "static_assert(RhsJit::d == " + DD + ", \"d of the struct differs from the d passed to odef_rhs_compile\");\n";
   s += "static_assert(RhsJit::np == " + std::to_string(r.np) + ", \"np of the struct differs from the n_params passed to odef_rhs_compile\");\n";
+  s += kTimeFlag;
   s += "}  // namespace odef\n";
   s += "extern \"C\" unsigned long odef_jit_abi() { return odef::team_abi_stamp(); }\n";
   s += "extern \"C\" const odef::FieldLaunch* odef_jit_field() {\n  using namespace odef;\n  static const FieldLaunch t = {" + DD + ", ";
@@ -102,26 +109,28 @@ std::string module_source(const JitRhs& r, int q, int ek1, int mv, int ieks) {
 
 // What odef_rhs_compile builds for d > 10 (no lane kernel exists to try the text on): the vector field in double, in
 // forward mode (the Jacobian EK1 needs when the struct has none), on Taylor jets (the initialisation), and its `analytic` if it has one
+// -- through the wrappers of rhs.h, so that a time-dependent field (has_time) is probed with its own signatures
 std::string probe_translation_unit(const JitRhs& r) {
   const std::string DD = std::to_string(r.d);
-  std::string s = "#include \"ek_lane.h\"\nnamespace odef {\n";
+  std::string s = "#include \"ek_lane.h\"\n#include \"errors_field.h\"\nnamespace odef {\n";
   s += r.source;
   s += "\nusing RhsJit = " + r.name + ";\n";
   s += "static_assert(RhsJit::d == " + DD + ", \"d of the struct differs from the d passed to odef_rhs_compile\");\n";
   s += "static_assert(RhsJit::np == " + std::to_string(r.np) + ", \"np of the struct differs from the n_params passed to odef_rhs_compile\");\n";
   s += "template <class R>\n__device__ void probe_analytic(const double (&u0)[R::d], const double* p, double t, double& acc) {\n"
-       "  if constexpr (HasAnalytic<R>::value) {\n    double ua[R::d];\n    R::analytic(u0, p, t, ua);\n    acc += ua[0];\n  }\n}\n";
+       "  if constexpr (HasAnalytic<R>::value) {\n    TruthAnalytic<R> tr(AnalyticArgs{u0, p, &t, 1, 0, 0, 1});\n    tr.init(0);\n    tr.at(0, 0);\n    acc += tr.get(0);\n  }\n}\n";
   s += "extern \"C\" __global__ void odef_jit_probe(const double* u, const double* p, double* out) {\n"
        "  constexpr int d = " + DD + ";\n"
        "  double uu[d], du[d], J[d][d], m0[2 * d];\n"
        "  for (int a = 0; a < d; ++a) uu[a] = u[a];\n"
-       "  RhsJit::f(uu, p, du);\n"
-       "  rhs_jacobian<RhsJit>(uu, p, J);\n"
-       "  taylor_init<RhsJit, 1>(uu, p, m0);\n"
+       "  rhs_eval<RhsJit>(uu, p, u[0], du);\n"
+       "  rhs_jacobian<RhsJit>(uu, p, u[0], J);\n"
+       "  taylor_init<RhsJit, 1>(uu, p, m0, u[0]);\n"
        "  double acc = 0.0;\n"
        "  probe_analytic<RhsJit>(uu, p, u[0], acc);\n"
        "  for (int a = 0; a < d; ++a) acc += du[a] + J[a][a] + m0[d + a];\n"
        "  out[0] = acc;\n}\n";
+  s += kTimeFlag;
   s += "}  // namespace odef\n";
   return s;
 }
@@ -243,7 +252,8 @@ void remove_tree(const std::string& dir) {  // the compiler's temporaries (flat 
 // process ("LLVM ERROR: Unsupported instruction") on the larger lane kernels (state dimension 14 and up), which the
 // offline compiler builds without complaint; a child process can only fail with a log.
 // $ODEFILTER_HIP_HIPCC overrides the compiler path (default: hipcc on PATH, then /opt/rocm/bin/hipcc).
-bool compile(const std::string& src, const std::string& include_dir, std::string& err, void** handle = nullptr) {
+// `has_time` != nullptr: receives whether the module's field is time-dependent (kTimeFlag).
+bool compile(const std::string& src, const std::string& include_dir, std::string& err, void** handle = nullptr, bool* has_time = nullptr) {
   err.clear();
   char tmpl[] = "/tmp/odef_jit_XXXXXX";
   const char* dir = mkdtemp(tmpl);
@@ -328,6 +338,7 @@ bool compile(const std::string& src, const std::string& include_dir, std::string
   }
   const std::string co = read_file(base + "/rhs-hip-amdgcn-amd-amdhsa-gfx950.out");
   const std::string stray = out_of_line_device_functions(co);
+  if (has_time) *has_time = co.find("odef_jit_time_flagILb1E") != std::string::npos;
   if (co.empty()) {
     err = "odef_rhs_compile: the compiler left no device code object (rhs-hip-amdgcn-amd-amdhsa-gfx950.out)";
   } else if (!stray.empty()) {
@@ -363,7 +374,7 @@ int jit_register(const char* name, const char* source, int d, int np, const char
   JitRhs r{name, source, include_dir ? include_dir : "", d, np};
   // compile the order-1 EK1 module (d <= 10; a probe kernel above) once now so that errors in the user's text surface here,
   // with the compiler log
-  if (!compile(d <= 10 ? module_source(r, 1, 1, 0, 0) : probe_translation_unit(r), r.include_dir, err)) return -1;
+  if (!compile(d <= 10 ? module_source(r, 1, 1, 0, 0) : probe_translation_unit(r), r.include_dir, err, nullptr, &r.has_time)) return -1;
   std::lock_guard<std::mutex> lk(g_mu);
   g_rhs.push_back(std::move(r));
   return kJitFirstId + (int)g_rhs.size() - 1;
@@ -376,6 +387,12 @@ bool jit_lookup(int rhs_id, int* d, int* np) {
   *d = g_rhs[k].d;
   *np = g_rhs[k].np;
   return true;
+}
+
+bool jit_has_time(int rhs_id) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  const int k = rhs_id - kJitFirstId;
+  return k >= 0 && k < (int)g_rhs.size() && g_rhs[k].has_time;
 }
 
 const FieldLaunch* jit_field(int rhs_id, int q, int ek1, int mv, int ieks, unsigned long abi_stamp, std::string& err) {

@@ -45,6 +45,7 @@ const FieldLaunch* field_lorenz63();
 const FieldLaunch* field_lotka_volterra();
 const FieldLaunch* field_vanderpol();
 const FieldLaunch* field_linear();
+const FieldLaunch* field_forced();  // time-dependent: f(u, p, t)
 const FieldLaunch* field_pleiades();  // d = 28 (BASELINE config 4)
 const FieldLaunch* field_lorenz96();  // d = 16: the same kernels on a second shape
 const FieldLaunch* field_launch(int rhs_id);  // the compiled-in fields; nullptr for any other id

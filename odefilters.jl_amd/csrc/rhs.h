@@ -193,12 +193,14 @@ struct HasJac<RHS, odef_void_t<decltype(&RHS::jac)>> { static constexpr bool val
 
 // Optional: `analytic(u0, p, t, out)`, the closed-form solution at the absolute time t (DiffEqBase's `f.analytic(u0, p, t)`), written
 // once in the scalar type like `f`.  A field that has one gets solution errors on the device (errors_field.h).
+// A solution that depends on the initial time takes it too: `analytic(u0, p, t0, t, out)` (the time of the first record).
 template <class RHS, class = void>
 struct HasAnalytic { static constexpr bool value = false; };
 template <class RHS>
 struct HasAnalytic<RHS, odef_void_t<decltype(&RHS::template analytic<double>)>> { static constexpr bool value = true; };
 
-// J = df/du at u: the vector field's own `jac` when it has one, forward-mode differentiation of `f` otherwise
+// J = df/du at u: the vector field's own `jac` when it has one, forward-mode differentiation of `f` otherwise (autonomous
+// fields; the form with a time follows)
 template <class RHS>
 __device__ inline void rhs_jacobian(const double (&u)[RHS::d], const double* p, double (&J)[RHS::d][RHS::d]) {
   constexpr int d = RHS::d;
@@ -212,6 +214,47 @@ __device__ inline void rhs_jacobian(const double (&u)[RHS::d], const double* p, 
       ud[a].g[a] = 1.0;
     }
     RHS::f(ud, p, fd);
+#pragma unroll
+    for (int r = 0; r < d; ++r)
+#pragma unroll
+      for (int a = 0; a < d; ++a) J[r][a] = fd[r].g[a];
+  }
+}
+
+// Optional: `static constexpr bool has_time = true;` -- a time-dependent field f(u, p, t) (the reference evaluates f and f.jac at
+// the step's new time, src/perform_step.jl:106,117).  Such a field provides
+//   template <class T> f(const T (&u)[d], const double* p, T t, T (&du)[d])       t: the absolute time, where `analytic` has it
+//   jac(const double (&u)[d], const double* p, double t, double (&J)[d][d])       (optional, as for an autonomous field)
+// rhs_eval / rhs_jacobian below are the only places that know both signatures.  The lane and row-team kernels carry the time
+// (DESIGN.md 3.14); the workgroup-per-trajectory kernels do not and refuse such a field at compile time.
+template <class RHS, class = void>
+struct HasTime { static constexpr bool value = false; };
+template <class RHS>
+struct HasTime<RHS, std::enable_if_t<RHS::has_time>> { static constexpr bool value = true; };
+
+// du = f(u, p, t); an autonomous field is not handed `t`
+template <class RHS, class T>
+__device__ inline void rhs_eval(const T (&u)[RHS::d], const double* p, T t, T (&du)[RHS::d]) {
+  if constexpr (HasTime<RHS>::value) RHS::f(u, p, t, du);
+  else RHS::f(u, p, du);
+}
+
+// J = df/du at (u, t), `t` a plain double in forward mode too
+template <class RHS>
+__device__ inline void rhs_jacobian(const double (&u)[RHS::d], const double* p, double t, double (&J)[RHS::d][RHS::d]) {
+  constexpr int d = RHS::d;
+  if constexpr (!HasTime<RHS>::value) {
+    rhs_jacobian<RHS>(u, p, J);
+  } else if constexpr (HasJac<RHS>::value) {
+    RHS::jac(u, p, t, J);
+  } else {
+    Dual<d> ud[d], fd[d];
+#pragma unroll
+    for (int a = 0; a < d; ++a) {
+      ud[a] = Dual<d>(u[a]);
+      ud[a].g[a] = 1.0;
+    }
+    RHS::f(ud, p, Dual<d>(t), fd);
 #pragma unroll
     for (int r = 0; r < d; ++r)
 #pragma unroll
@@ -327,6 +370,31 @@ struct RhsLinear {  // test/convergence.jl:9-14, test/state_init.jl:12-17
   }
 };
 
+// A forced linear pair, the time-dependent field of the registry: t enters f (u0) and the Jacobian (u1).
+//   u0' = p0 u0 + p1 t,   u1' = p2 t u1
+struct RhsForced {
+  static constexpr int d = 2, np = 3, id = 7;
+  static constexpr const char* name = "RhsForced";
+  static constexpr bool has_time = true;
+  template <class T>
+  __device__ static void f(const T (&u)[2], const double* p, T t, T (&du)[2]) {
+    du[0] = p[0] * u[0] + p[1] * t;
+    du[1] = p[2] * t * u[1];
+  }
+  __device__ static void jac(const double (&/*u*/)[2], const double* p, double t, double (&J)[2][2]) {
+    J[0][0] = p[0];
+    J[0][1] = 0.0;
+    J[1][0] = 0.0;
+    J[1][1] = p[2] * t;
+  }
+  // u0(t) = (u0 + p1 t0 / p0 + p1 / p0^2) e^{p0 (t - t0)} - p1 t / p0 - p1 / p0^2,   u1(t) = u1 e^{p2 (t^2 - t0^2) / 2}
+  template <class T>
+  __device__ static void analytic(const T (&u0)[2], const double* p, T t0, T t, T (&out)[2]) {
+    const double a = p[0], b = p[1], c = b / (a * a);
+    out[0] = (u0[0] + b * t0 / a + c) * exp(a * (t - t0)) - b * t / a - c;
+    out[1] = u0[1] * exp(0.5 * p[2] * (t * t - t0 * t0));
+  }
+};
 
 // Lorenz-96 with 16 variables, u_i' = (u_{i+1} - u_{i-2}) u_{i-1} - u_i + F, p = (F): the second vector field of the
 // workgroup-per-trajectory kernels (state dimension 16 (q+1): 64 at order 3, 96 at order 5).  It has none of Pleiades' team

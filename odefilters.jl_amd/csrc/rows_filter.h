@@ -108,6 +108,7 @@ struct RowsScale {
 };
 
 // IEKS: the Jacobian at the linearisation point `u_lin` of `run` (team-uniform, every lane its copy), as EKStep.
+// A time-dependent field (HasTime<RHS>): `aux` is a StepAuxTime<StepAux>, f and the Jacobian are evaluated at `aux.tnew`.
 template <class RHS, int q, bool IS_EK1, bool IEKS = false>
 struct RowsStep {
   static_assert(!IEKS || IS_EK1, "IEKS is an EK1 step");
@@ -122,10 +123,11 @@ struct RowsStep {
 
   // One attempted step, in place: (m, xr) = cache.x -> cache.x_filt (src/perform_step.jl:27-76).
   // err_scale[r] = sqrt(diag(H (sigma2_local Q) H')) (src/perform_step.jl:148-158).
+  template <class Aux = StepAux>
   __device__ static inline void run(const PriorConsts& pc, const RowsConsts<d, NB>& lc, const RowsScale<d, NB>& sc,
                                     const double* __restrict__ pl, int fixed_diffusion, bool want_loglik, int success_iter,
                                     double prev_global, const tv::Lds& lds, TV& m, TV (&xr)[D], double (&err_scale)[d],
-                                    StepAux& aux, int qm_lds_off = -1,  // qm_lds_off >= 0: the lanes' rows of Q are in LDS there
+                                    Aux& aux, int qm_lds_off = -1,  // qm_lds_off >= 0: the lanes' rows of Q are in LDS there
                                     const double (*u_lin)[d] = nullptr) {
     const double pi0 = sc.pijv[0], pi1 = sc.pijv[1];
     // x~ = P x (src/perform_step.jl:36-38)
@@ -145,14 +147,15 @@ struct RowsStep {
     tv::bcast_lanes<d, d>(mp, e1);
 #pragma unroll
     for (int a = 0; a < d; ++a) up[a] = pi0 * up[a];
-    RHS::f(up, pl, du);
+    if constexpr (HasTime<RHS>::value) rhs_eval<RHS>(up, pl, aux.tnew, du);
+    else RHS::f(up, pl, du);
 #pragma unroll
     for (int a = 0; a < d; ++a) z[a] = pi1 * e1[a] - du[a];
     double H0[d][d];  // H = (E1 - J E0) P^-1 -> blocks H0 = -J pi0, H1 = pi1 I;  EK0: H0 = 0
     if constexpr (IS_EK1) {
       double Jm[d][d];
-      if constexpr (IEKS) rhs_jacobian<RHS>(*u_lin, pl, Jm);  // src/perform_step.jl:111-113
-      else rhs_jacobian<RHS>(up, pl, Jm);
+      if constexpr (IEKS) rhs_jacobian<RHS>(*u_lin, pl, step_time<RHS>(aux), Jm);  // src/perform_step.jl:111-113
+      else rhs_jacobian<RHS>(up, pl, step_time<RHS>(aux), Jm);
 #pragma unroll
       for (int r = 0; r < d; ++r)
 #pragma unroll
@@ -395,7 +398,9 @@ __device__ inline void rows_initial_state(const FilterParams& P, long i, double 
 #pragma unroll
   for (int a = 0; a < d; ++a) u0[a] = P.u0[(size_t)a * P.N + i];
   double m0[D];
-  taylor_init<RHS, q>(u0, pl, m0);  // src/state_initialization.jl:2-53, every lane for itself
+  // src/state_initialization.jl:2-53, every lane for itself
+  if constexpr (HasTime<RHS>::value) taylor_init<RHS, q>(u0, pl, m0, P.t0);
+  else taylor_init<RHS, q>(u0, pl, m0);
   m = tv::lane_table(m0, D, 0.0);
 #pragma unroll
   for (int c = 0; c < D; ++c) xr[c] = tv::splat(0.0);
@@ -437,8 +442,9 @@ __device__ inline void rows_filter_fixed(const FilterParams& P, const RowsTeam& 
       cur_tab = ti;
     }
     double es[d];
-    StepAux aux;
+    StepAuxFor<RHS, StepAux> aux;
     aux.chol_fix = 0;
+    if constexpr (HasTime<RHS>::value) aux.tnew = uniform_load(P.tgrid + n + 1);  // wave-uniform, a scalar load
     double ul[d];
     if constexpr (IEKS) {
 #pragma unroll
@@ -538,8 +544,9 @@ __device__ inline void rows_filter_adaptive(const FilterParams& P, const RowsTea
       const tv::TV m_old = m;
       tv::lds_put_private<D>(lds, kOldOff, xr);  // the state before the attempt: needed again only when it is rejected
       double es[d];
-      StepAux aux;
+      StepAuxFor<RHS, StepAux> aux;
       aux.chol_fix = 0;
+      if constexpr (HasTime<RHS>::value) aux.tnew = t + h;  // this attempt's new time: what T receives when it is accepted
       S::run(P.pc, lc, sc, pl, P.fixed_diffusion, P.want_loglik != 0, naccept, gdiff, lds, m, xr, es, aux, kQmOff);
       // DiffEqBase.calculate_residuals! + ODE_DEFAULT_NORM (src/perform_step.jl:78-84)
       double unew[d];

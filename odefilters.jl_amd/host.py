@@ -27,9 +27,10 @@ EK0_ID, EK1_ID, IEKS_ID = 0, 1, 2
 DIFFUSION = {"dynamic": 0, "fixed": 1, "fixedMAP": 2, "dynamicMV": 3, "fixedMV": 4}
 # the diagonal ("multivariate") models: one diffusion per state component, EK0 on the lane kernels only (include/odefilter.h)
 MV_DIFFUSIONS = ("dynamicMV", "fixedMV")
-RHS = {"fhn": 0, "lorenz63": 1, "lotka_volterra": 2, "vanderpol": 3, "linear": 4, "pleiades": 5, "lorenz96": 6}
+RHS = {"fhn": 0, "lorenz63": 1, "lotka_volterra": 2, "vanderpol": 3, "linear": 4, "pleiades": 5, "lorenz96": 6,
+       "forced": 7}
 RHS_DIMS = {"fhn": (2, 3), "lorenz63": (3, 3), "lotka_volterra": (2, 4), "vanderpol": (2, 1), "linear": (2, 2),
-            "pleiades": (28, 0), "lorenz96": (16, 1)}
+            "pleiades": (28, 0), "lorenz96": (16, 1), "forced": (2, 3)}
 SAVE_FINAL, SAVE_EVERYSTEP = 0, 1
 RETCODES = {0: "Success", 1: "MaxIters", 2: "DtLessThanMin", 3: "Unstable", 4: "Unstable"}
 (F_MEAN, F_COV_TRIL, F_DIFFUSION, F_T, F_LOGLIK, F_NACCEPT, F_NREJECT, F_NF, F_NJAC, F_NSAVED, F_RETCODE,
@@ -346,7 +347,13 @@ def compile_rhs(name: str, source: str, d: int, n_params: int, struct_name: Opti
     closure `f` (+ `jac`) the reference calls at src/perform_step.jl:106,116-121.  `source` defines a struct
     `struct_name` (default: `name`) with the interface of csrc/rhs.h.  Afterwards `name` can be used wherever a
     compiled-in vector field name is accepted (`ODEProblem(name, ...)`, `Context(name, ...)`).  Raises OdefError with
-    the compiler log when the text does not compile."""
+    the compiler log when the text does not compile.
+
+    A time-dependent field f(u, p, t) sets `static constexpr bool has_time = true;` and takes the absolute time behind
+    `p`: `f(const T (&u)[d], const double* p, T t, T (&du)[d])`, `jac(u, p, double t, J)` (optional), and `analytic(u0, p,
+    t0, t, out)` (optional).  The step evaluates it at its new time, the Taylor initialisation differentiates in t too;
+    `solve` takes no new keyword.  It runs on the lane and row-team kernels (d <= 10, d (q + 1) <= 20): above, creating
+    the context raises OdefError."""
     lib = load_library()
     rid = C.c_int32(-1)
     inc = os.path.join(_HERE, "csrc").encode()
