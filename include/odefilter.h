@@ -35,6 +35,8 @@
  *   odef_ibm / odef_preconditioner  ibm(d,q), preconditioner(T,d,q)              src/priors.jl:7-59,
  *                                                                                src/preconditioning.jl:1-17
  *   odef_errors_field ids           sol.errors, sol.u_analytic                    src/solution.jl:10-11,68-74,129-130
+ *   odef_data_field ids             nothing in this version of the reference (later ones ship it as fenrir_data_loglik): the
+ *                                   marginal log-likelihood of noisy observations under the posterior, per trajectory
  *   odef_summary_field ids          nothing in the reference: per-time mean and covariance of the ensemble's Gaussian mixture,
  *                                   reduced on the device and read with odef_get (see odef_summary_field)
  *   odef_group_* / odef_allgather   nothing in the reference (it has no ensemble and no distributed code):
@@ -215,6 +217,42 @@ typedef enum {
   ODEF_E_REFERENCE = 144 /* odef_bind_device only */
 } odef_errors_field;
 
+/* Data log-likelihood of noisy observations per trajectory, on the device (nothing leaves it but 16 N bytes).  The filter records
+ * (m_k, Sigma_k) of a FIXED grid and the backward transitions of the RTS smoother define a Gauss-Markov posterior over the path;
+ * the marginal likelihood of observations y_j = H x(t_{k_j}) + N(0, R) under it is one backward sweep (the "Fenrir" likelihood of
+ * Tronarp, Bosch and Hennig 2022), k = n_save - 1 down to the first observed save, xi starting as the last filter record:
+ *     k < n_save - 1, h = t_{k+1} - t_k != 0, in the coordinates preconditioned with P(h) as odef_smooth does:
+ *         B = A Sigma_k A' + sigma2_k Q;  G = Sigma_k A' B^-1;  xi.m <- m_k + G (xi.m - A m_k);  xi.P <- Sigma_k + G (xi.P - B) G'
+ *         (sigma2_k: DIFFUSION[k + 1], the value odef_smooth uses for that step; a non-positive pivot of B drops its direction)
+ *     k = k_j:  v = y_j - H xi.m;  S = H xi.P H' + R;  l += -1/2 (v' S^-1 v + log det S + o log 2 pi);  q += v' S^-1 v
+ *               K = xi.P H' S^-1;  xi.m += K v;  xi.P -= K S K'
+ *   ODEF_L_DATA_LOGLIK       l  double [N]     odef_field_bytes / odef_get / odef_get_device
+ *   ODEF_L_DATA_MAHALANOBIS  q  double [N]     chi^2 with M o degrees of freedom for a calibrated model
+ * Inputs, device memory bound with odef_bind_device (read only, never written; NULL lets one go); M and o follow from the byte counts:
+ *   ODEF_L_OBS_SAVE       int64  [M]           observed save indices k_1 < ... < k_M in 0 .. n_save - 1 (save 0 may be observed)
+ *   ODEF_L_OBS_COMPONENT  int64  [o]           observed state components c_1 < ... < c_o in 0 .. d - 1: H is those rows of E0
+ *   ODEF_L_OBS_VALUE      double [M][o]        shared by the ensemble, or [M][o][N] per trajectory (told by the byte count, as for p)
+ *   ODEF_L_OBS_NOISE      double [o]           variances r > 0, R = diag r
+ * The first request runs the pass on the context's stream (one launch, one lane per trajectory; SAVE, COMPONENT and NOISE are copied
+ * to the host and validated there) and caches both outputs; two requests agree bit for bit.  The cache is dropped by odef_solve_*,
+ * odef_set_problem*, a bind of any of the four inputs, and a bind or odef_get_device of MEAN, COV_TRIL, DIFFUSION or T (the pointer
+ * handed out is writable).  Refused with a message: before a solve; after an ADAPTIVE solve (observation times are per ensemble, the
+ * grid per trajectory); the MV diffusion models; a (d, q) without a kernel (built for d <= 4, q <= 5, d (q + 1) <= 20); an input
+ * missing; byte counts that do not agree; saves or components that are not strictly increasing or out of range; a noise variance
+ * that is not finite and positive; a context that kept only the final state.  A non-positive pivot of S or a NaN in a record the
+ * sweep reads gives NaN for that trajectory only; a trajectory whose RETCODE is not Success still gets a number.
+ * odef_kernel_time_ms / odef_kernel_name report the last pass as which = 4; its n_launches counts the passes launched since the
+ * context was created (a request served from the cache leaves it unchanged). */
+typedef enum {
+  ODEF_L_BASE = 192,
+  ODEF_L_DATA_LOGLIK = 192,
+  ODEF_L_DATA_MAHALANOBIS = 193,
+  ODEF_L_OBS_SAVE = 200,      /* odef_bind_device only */
+  ODEF_L_OBS_COMPONENT = 201, /* odef_bind_device only */
+  ODEF_L_OBS_VALUE = 202,     /* odef_bind_device only */
+  ODEF_L_OBS_NOISE = 203      /* odef_bind_device only */
+} odef_data_field;
+
 /* POD mirror of the reference's keyword structs (src/algorithms.jl:23-28,46-51) plus the
  * ensemble shape.  Zero-initialise, set struct_size = sizeof(odef_config). */
 typedef struct {
@@ -347,7 +385,8 @@ int odef_get_device(odef_ctx* ctx, int field, void** dev_ptr, size_t* bytes);
 int odef_bind_device(odef_ctx* ctx, int field, void* dev_ptr, size_t bytes);
 int odef_synchronize(odef_ctx* ctx);
 
-/* Device time of the last filter (which=0) / smoother (which=1) / ensemble-summary (which=2) / solution-error (which=3) launch, measured with
+/* Device time of the last filter (which=0) / smoother (which=1) / ensemble-summary (which=2) / solution-error (which=3) /
+ * data-likelihood (which=4) launch, measured with
  * hipEvents on the launch stream; n_launches = kernels launched by that call. */
 int odef_kernel_time_ms(odef_ctx* ctx, int which, float* ms, int* n_launches);
 /* Name of the kernel that call launched (the dominant one of a multi-kernel pass), as a profiler prints it, e.g.

@@ -63,6 +63,15 @@ const E_SMOOTH_CHI2 = 139
 const E_SMOOTH_NUSED = 140
 const E_SMOOTH_U_ANALYTIC = 141
 const E_REFERENCE = 144
+# data log-likelihood of noisy observations per trajectory (odef_data_field, include/odefilter.h): two outputs [N], four inputs
+# that odef_bind_device alone takes.  UNTESTED like the rest of this file.
+const L_BASE = 192
+const L_DATA_LOGLIK = 192
+const L_DATA_MAHALANOBIS = 193
+const L_OBS_SAVE = 200
+const L_OBS_COMPONENT = 201
+const L_OBS_VALUE = 202
+const L_OBS_NOISE = 203
 const RETCODES = (:Success, :MaxIters, :DtLessThanMin, :Unstable, :Unstable)
 
 """Ensemble algorithm: all trajectories of an `EnsembleProblem` on one GPU (`devices` empty / one entry) or sharded
@@ -128,6 +137,21 @@ function solution_errors(ctx, n_traj::Integer; source::Integer=0)
     errs = Dict(:final => fetch(ctx, id(0), Float64, n_traj), :l2 => fetch(ctx, id(1), Float64, n_traj),
                 Symbol("l∞") => fetch(ctx, id(2), Float64, n_traj), :chi2 => fetch(ctx, id(3), Float64, n_traj))
     return errs, fetch(ctx, id(4), Int64, n_traj)
+end
+
+"""
+    data_loglik(ctx, n_traj, saves, comps, values, noise) -> (loglik, mahalanobis)
+
+Log-likelihood of noisy observations under the posterior of the last fixed-grid solve of the live context `ctx`, per trajectory,
+reduced on the device (later versions of the reference: `fenrir_data_loglik`).  The four arguments are DEVICE pointers that stay
+the caller's: `saves` Int64 [M] (0-based save indices, increasing), `comps` Int64 [o] (0-based state components, increasing),
+`values` Float64 [M][o] or [M][o][N], `noise` Float64 [o] variances, each given as `(ptr, bytes)`.  UNTESTED.
+"""
+function data_loglik(ctx, n_traj::Integer, saves, comps, values, noise)
+    for (f, (ptr, bytes)) in ((L_OBS_SAVE, saves), (L_OBS_COMPONENT, comps), (L_OBS_VALUE, values), (L_OBS_NOISE, noise))
+        check(ccall((:odef_bind_device, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Csize_t), ctx, f, ptr, bytes), ctx)
+    end
+    return fetch(ctx, L_DATA_LOGLIK, Float64, n_traj), fetch(ctx, L_DATA_MAHALANOBIS, Float64, n_traj)
 end
 
 """

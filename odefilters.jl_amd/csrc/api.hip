@@ -19,6 +19,7 @@
 #include "launch.h"
 #include "summary.h"
 #include "errors.h"
+#include "datalik.h"
 
 using namespace odef;
 
@@ -74,13 +75,15 @@ struct odef_ctx {
   size_t ws_cap = 0;
   Buf f[ODEF_F_COUNT_];
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  float ms[4] = {0.f, 0.f, 0.f, 0.f};
-  int nl[4] = {0, 0, 0, 0};
-  char kname[4][192] = {"", "", "", ""};  // kernel of the last filter / smoother / ensemble-summary / solution-error pass (odef_kernel_name)
+  float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  int nl[5] = {0, 0, 0, 0, 0};
+  char kname[5][192] = {"", "", "", "", ""};  // kernel of the last filter / smoother / ensemble-summary / solution-error / data-likelihood pass (odef_kernel_name)
   SummaryState summary;  // cached ensemble summaries of the filter, smoothed and dense records (odef_summary_field)
   ErrorsState errors;    // cached solution errors of the filter and smoothed records (odef_errors_field)
   const double* err_ref = nullptr;  // ODEF_E_REFERENCE: the bound truth [n_save][d][N] (caller memory, read only)
   size_t err_ref_bytes = 0;
+  DataLikState datalik;  // cached data log-likelihood of the filter records (odef_data_field)
+  Buf obs[4];            // ODEF_L_OBS_SAVE / COMPONENT / VALUE / NOISE: caller memory, read only
   // odef_group runs its shards concurrently: with `defer` set, odef_solve_* / odef_smooth return after the launch and
   // complete_pending() does the wait + timing (pending: 1 = filter, 2 = smoother)
   bool defer = false;
@@ -261,6 +264,7 @@ void invalidate_summary(odef_ctx* c, int source) {
 }
 void invalidate_summaries(odef_ctx* c) {
   for (int k = 0; k < 3; ++k) invalidate_summary(c, k);
+  c->datalik.valid = false;  // (every caller changes the filter records or the problem)
 }
 
 // number of times of a summary source, or -1 with the reason in odef_last_error
@@ -387,6 +391,69 @@ int errors_field(odef_ctx* c, int field, const char* who, void** ptr, size_t* by
     if (rc) return fail(c, "%s: %s", who, err.c_str());
   }
   *ptr = truth ? (void*)ec.truth : quantity == ODEF_E_NUSED - ODEF_E_BASE ? (void*)ec.nused : (void*)ec.val[quantity];
+  return 0;
+}
+
+// odef_data_field: the two outputs, and the four inputs that odef_bind_device alone takes
+bool is_datalik_output(int field) { return field == ODEF_L_DATA_LOGLIK || field == ODEF_L_DATA_MAHALANOBIS; }
+bool is_datalik_input(int field) { return field >= ODEF_L_OBS_SAVE && field <= ODEF_L_OBS_NOISE; }
+// the records the pass reads: a caller that binds them, or takes their (writable) device pointer, may change them
+bool is_datalik_record(int field) {
+  return field == ODEF_F_MEAN || field == ODEF_F_COV_TRIL || field == ODEF_F_DIFFUSION || field == ODEF_F_T;
+}
+
+// 0 when the data log-likelihood can be computed, else -1 with the reason in odef_last_error (no device is touched)
+int datalik_check(const odef_ctx* c, const char* who) {
+  if (!c->solved) return fail(c, "%s: data log-likelihood requested before a solve (call odef_solve_* first)", who);
+  if (c->adaptive)
+    return fail(c, "%s: data log-likelihood after an adaptive solve: the observation times are per ensemble, the grid of an adaptive "
+                   "solve is per trajectory; solve on a fixed grid that contains the observation times", who);
+  if (is_mv(c->cfg.diffusion))
+    return fail(c, "%s: data log-likelihood is built for the scalar diffusion models, not :dynamicMV / :fixedMV", who);
+  if (team_path(c) || !datalik_has(c->d, c->q))
+    return fail(c, "%s: data log-likelihood has no kernel for (d, q) = (%d, %d); built for d <= 4, q <= 5, d (q + 1) <= 20", who, c->d, c->q);
+  if (c->cfg.save_mode != ODEF_SAVE_EVERYSTEP || c->n_save < 2)
+    return fail(c, "%s: data log-likelihood needs the records of every step, this context kept only the final state "
+                   "(ODEF_SAVE_EVERYSTEP)", who);
+  static const char* const kName[4] = {"ODEF_L_OBS_SAVE", "ODEF_L_OBS_COMPONENT", "ODEF_L_OBS_VALUE", "ODEF_L_OBS_NOISE"};
+  for (int k = 0; k < 4; ++k)
+    if (!c->obs[k].ptr) return fail(c, "%s: data log-likelihood input missing: bind %s with odef_bind_device", who, kName[k]);
+  return 0;
+}
+
+// the cached array of a data log-likelihood field; the first request after the records or an input changed runs the pass
+int datalik_field(odef_ctx* c, int field, const char* who, void** ptr, size_t* bytes) {
+  if (datalik_check(c, who)) return -1;
+  if (set_device(c)) return -1;
+  if (!c->datalik.valid) {
+    DataLikRequest r;
+    std::memset(&r, 0, sizeof r);
+    r.pc = &c->pc;
+    r.N = c->cfg.n_traj;
+    r.n_save = c->n_save;
+    r.d = c->d;
+    r.q = c->q;
+    r.ptab = c->d_ptab;
+    r.tab_idx = c->d_tab_idx;
+    r.hs = c->d_hs;
+    r.mean = (const double*)c->f[ODEF_F_MEAN].ptr;
+    r.cov = (const double*)c->f[ODEF_F_COV_TRIL].ptr;
+    r.diff = (const double*)c->f[ODEF_F_DIFFUSION].ptr;
+    if (!r.mean || !r.cov || !r.diff || !r.hs) return fail(c, "%s: the filter records hold no data", who);
+    r.obs_save = c->obs[0].ptr;
+    r.obs_comp = c->obs[1].ptr;
+    r.obs_val = (const double*)c->obs[2].ptr;
+    r.obs_noise = (const double*)c->obs[3].ptr;
+    r.save_bytes = c->obs[0].bytes;
+    r.comp_bytes = c->obs[1].bytes;
+    r.val_bytes = c->obs[2].bytes;
+    r.noise_bytes = c->obs[3].bytes;
+    std::string err;
+    if (datalik_run(c->datalik, r, c->stream, &c->ms[4], &c->nl[4], c->kname[4], sizeof c->kname[4], err))
+      return fail(c, "%s: %s", who, err.c_str());
+  }
+  *ptr = c->datalik.out[field - ODEF_L_BASE];
+  *bytes = (size_t)c->cfg.n_traj * sizeof(double);
   return 0;
 }
 
@@ -606,6 +673,7 @@ void odef_destroy(odef_ctx* c) {
   if (c->d_tab_idx) (void)hipFree(c->d_tab_idx);
   summary_free(c->summary);
   errors_free(c->errors);
+  datalik_free(c->datalik);
   for (int k = 0; k < 4; ++k)
     if (c->ev[k]) (void)hipEventDestroy(c->ev[k]);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1106,6 +1174,11 @@ int odef_field_bytes(const odef_ctx* c, int field, size_t* bytes) {
     *bytes = errors_bytes(c, (field - ODEF_E_BASE) % 8);
     return 0;
   }
+  if (c && bytes && is_datalik_output(field)) {
+    if (datalik_check(c, "odef_field_bytes")) return -1;
+    *bytes = (size_t)c->cfg.n_traj * sizeof(double);
+    return 0;
+  }
   if (!c || !bytes || field < 0 || field >= ODEF_F_COUNT_) return -1;
   if (field == ODEF_F_T && !c->adaptive) { *bytes = c->tgrid.size() ? (size_t)c->n_save * sizeof(double) : 0; return 0; }
   *bytes = c->f[field].valid;
@@ -1123,10 +1196,10 @@ int odef_get(odef_ctx* c, int field, void* host_dst, size_t bytes) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
   }
-  if (is_errors_field(field)) {
+  if (is_errors_field(field) || is_datalik_output(field)) {
     void* src = nullptr;
     size_t have = 0;
-    if (errors_field(c, field, "odef_get", &src, &have)) return -1;
+    if (is_datalik_output(field) ? datalik_field(c, field, "odef_get", &src, &have) : errors_field(c, field, "odef_get", &src, &have)) return -1;
     if (bytes != have) return fail(c, "odef_get: field %d holds %zu bytes, caller asked for %zu", field, have, bytes);
     HIPCHK(c, hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1154,6 +1227,8 @@ int odef_get_device(odef_ctx* c, int field, void** dev_ptr, size_t* bytes) {
   if (!c || !dev_ptr || !bytes) return fail(c, "odef_get_device: null argument");
   if (is_summary_field(field)) return summary_field(c, field, "odef_get_device", dev_ptr, bytes);
   if (is_errors_field(field)) return errors_field(c, field, "odef_get_device", dev_ptr, bytes);
+  if (is_datalik_output(field)) return datalik_field(c, field, "odef_get_device", dev_ptr, bytes);
+  if (is_datalik_record(field)) c->datalik.valid = false;  // the pointer handed out is writable
   if (field < 0 || field >= ODEF_F_COUNT_) return fail(c, "odef_get_device: unknown field %d", field);
   const Buf& b = c->f[field];
   if (!b.ptr || !b.valid) return fail(c, "odef_get_device: field %d holds no data yet", field);
@@ -1170,7 +1245,19 @@ int odef_bind_device(odef_ctx* c, int field, void* dev_ptr, size_t bytes) {
     for (int k = 0; k < 2; ++k) c->errors.src[k].valid = false;
     return 0;
   }
+  if (is_datalik_input(field)) {  // the observations of the data log-likelihood: caller memory, read only; NULL lets it go
+    Buf& b = c->obs[field - ODEF_L_OBS_SAVE];
+    b = Buf{};
+    if (dev_ptr) {
+      b.ptr = dev_ptr;
+      b.bytes = bytes;
+      b.bound = true;
+    }
+    c->datalik.valid = false;
+    return 0;
+  }
   if (field < 0 || field >= ODEF_F_COUNT_ || field == ODEF_F_U0) return fail(c, "odef_bind_device: field %d cannot be bound", field);
+  if (is_datalik_record(field)) c->datalik.valid = false;
   if (field == ODEF_F_LINEARIZE_AT && dev_ptr && c->cfg.alg != ODEF_IEKS)
     return fail(c, "odef_bind_device: ODEF_F_LINEARIZE_AT belongs to an IEKS context (alg = ODEF_IEKS)");
   if (set_device(c)) return -1;
@@ -1197,13 +1284,13 @@ int odef_synchronize(odef_ctx* c) {
 }
 
 int odef_kernel_name(odef_ctx* c, int which, char* buf, size_t n) {
-  if (!c || which < 0 || which > 3 || !buf || n == 0) return -1;
+  if (!c || which < 0 || which > 4 || !buf || n == 0) return -1;
   std::snprintf(buf, n, "%s", c->kname[which]);
   return 0;
 }
 
 int odef_kernel_time_ms(odef_ctx* c, int which, float* ms, int* n_launches) {
-  if (!c || which < 0 || which > 3 || !ms) return -1;
+  if (!c || which < 0 || which > 4 || !ms) return -1;
   *ms = c->ms[which];
   if (n_launches) *n_launches = c->nl[which];
   return 0;

@@ -1,0 +1,47 @@
+// Data log-likelihood of noisy observations per trajectory on the device (include/odefilter.h, odef_data_field):
+// the marginal likelihood of y_j = H x(t_{k_j}) + N(0, diag r) under the Gauss-Markov posterior that the filter records and the
+// smoother's backward transitions define, by one backward sweep over the records of a fixed grid.  Host-side interface of
+// datalik.hip; this header includes none of the step headers, so that no filter / smoother kernel depends on it.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <string>
+
+namespace odef {
+
+struct PriorConsts;  // ek_math.h
+
+struct DataLikState {
+  double* out[2] = {nullptr, nullptr};  // DATA_LOGLIK, DATA_MAHALANOBIS [N], device memory owned by the context
+  bool valid = false;
+  hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+struct DataLikRequest {
+  const PriorConsts* pc;
+  long N, n_save;
+  int d, q;
+  const double* ptab;   // the grid's tables, as the smoother takes them
+  const int* tab_idx;
+  const double* hs;
+  const double* mean;   // filter records, ABI layout
+  const double* cov;
+  const double* diff;
+  const void* obs_save;    // [M] int64
+  const void* obs_comp;    // [o] int64
+  const double* obs_val;   // [M][o] or [M][o][N]
+  const double* obs_noise; // [o]
+  size_t save_bytes, comp_bytes, val_bytes, noise_bytes;
+};
+
+// true when data_loglik_kernel<d, q> is instantiated (d <= 4, q <= 5, d (q + 1) <= 20)
+bool datalik_has(int d, int q);
+// Copies saves, components and noise to the host (M + 2 o words) and validates them, runs the pass on `stream` (one launch) into
+// `st` and waits.  Returns 0, or -1 with `err` set.
+int datalik_run(DataLikState& st, const DataLikRequest& r, hipStream_t stream, float* ms, int* n_launches, char* kname, size_t kname_n,
+                std::string& err);
+void datalik_free(DataLikState& st);
+
+}  // namespace odef

@@ -86,6 +86,66 @@ def errors_field(source: int, quantity: int) -> int:
 
 def _is_errors_field(f: int) -> bool:
     return E_BASE <= f < E_BASE + 16 and (f - E_BASE) % 8 < 6
+
+
+# data log-likelihood of noisy observations per trajectory (odef_data_field, include/odefilter.h)
+L_BASE = 192
+L_DATA_LOGLIK, L_DATA_MAHALANOBIS = 192, 193
+L_OBS_SAVE, L_OBS_COMPONENT, L_OBS_VALUE, L_OBS_NOISE = 200, 201, 202, 203  # odef_bind_device only
+DATA_FIELDS = {
+    "ODEF_L_BASE": 192,
+    "ODEF_L_DATA_LOGLIK": 192, "ODEF_L_DATA_MAHALANOBIS": 193,
+    "ODEF_L_OBS_SAVE": 200, "ODEF_L_OBS_COMPONENT": 201, "ODEF_L_OBS_VALUE": 202, "ODEF_L_OBS_NOISE": 203,
+}
+K_DATA_LOGLIK = 4  # `which` of odef_kernel_time_ms / odef_kernel_name
+
+
+def _observation_arrays(t, d, N, times, data, noise_var, components):
+    """The four inputs of the data log-likelihood in the ABI layout, validated on the host: (saves int64 [M], comps int64 [o],
+    values [M, o] or [M, o, N], noise [o], per_trajectory).  `times` must equal entries of the save grid `t` exactly."""
+    t = np.asarray(t, np.float64).reshape(-1)
+    times = np.atleast_1d(np.asarray(times, np.float64))
+    if times.ndim != 1 or times.size == 0:
+        raise OdefError("data_loglik: times must be a non-empty 1-d array")
+    saves = np.searchsorted(t, times)
+    if np.any(saves >= t.size) or np.any(t[np.minimum(saves, t.size - 1)] != times):
+        bad = times[(saves >= t.size) | (t[np.minimum(saves, t.size - 1)] != times)]
+        raise OdefError(f"data_loglik: observation times must equal save times of the solution exactly; not on the grid: {bad[:4]}")
+    if np.any(np.diff(saves) <= 0):
+        raise OdefError("data_loglik: observation times must be strictly increasing")
+    comps = np.arange(d) if components is None else np.atleast_1d(np.asarray(components))
+    if comps.ndim != 1 or comps.size == 0 or not np.issubdtype(comps.dtype, np.integer):
+        raise OdefError("data_loglik: components must be a non-empty 1-d integer array")
+    if np.any(comps < 0) or np.any(comps >= d) or np.any(np.diff(comps) <= 0):
+        raise OdefError(f"data_loglik: components must be strictly increasing within 0 .. {d - 1}")
+    M, o = saves.size, comps.size
+    data = np.asarray(data, np.float64)
+    if data.shape == (M, o):
+        per_traj, values = False, np.ascontiguousarray(data)
+    elif data.shape == (N, M, o):
+        per_traj, values = True, np.ascontiguousarray(data.transpose(1, 2, 0))
+    else:
+        raise OdefError(f"data_loglik: data must have shape ({M}, {o}) or ({N}, {M}, {o}), got {data.shape}")
+    noise = np.asarray(noise_var, np.float64)
+    if noise.ndim == 0:
+        noise = np.full(o, float(noise))
+    if noise.shape != (o,):
+        raise OdefError(f"data_loglik: noise_var must be a scalar or have shape ({o},), got {noise.shape}")
+    if not np.all(np.isfinite(noise)) or np.any(noise <= 0):
+        raise OdefError("data_loglik: noise variances must be finite and positive")
+    return saves.astype(np.int64), comps.astype(np.int64), values, np.ascontiguousarray(noise), per_traj
+
+
+def _to_device(arrays, device):
+    """numpy arrays -> torch tensors on GPU `device` (kept alive by the caller while they are bound).  A process that uses this
+    brings up torch's HIP runtime before the library's first context (`torch.cuda.init()`), as tests/conftest.py does: brought up
+    second it has been seen to find no GPU."""
+    import torch
+
+    dev = torch.device("cuda", int(device) if device >= 0 else torch.cuda.current_device())
+    out = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in arrays]
+    torch.cuda.synchronize(dev)
+    return out
 MAX_ORDER = 5
 
 
@@ -209,6 +269,7 @@ class DeviceGroup:
         if self.lib.odef_group_create(C.byref(h), C.byref(cfg), n_devices, ids) != 0:
             raise OdefError(self.lib.odef_group_last_error(None).decode())
         self._h = h
+        self._devices = list(device_ids) if device_ids is not None else list(range(n_devices))
 
     def _chk(self, rc):
         if rc != 0:
@@ -305,6 +366,27 @@ class DeviceGroup:
         per-trajectory arrays are joined along the trajectory axis.  dict with "l∞", "l2", "final", "chi2" [N] and "nused"."""
         parts = [Context._solution_errors(self.lib, self.lib.odef_group_ctx(self._h, g), source) for g in range(self.G)]
         return {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
+    def data_loglik(self, times, data, noise_var, components=None):
+        """Data log-likelihood of the WHOLE ensemble (`EnsembleSolution.data_loglik`): the same observations go to every shard
+        through `odef_group_ctx`, per-trajectory values are split by `odef_group_shard`, every shard runs the pass on its own
+        device and the results are joined along the trajectory axis.  Returns (loglik [N], mahalanobis [N])."""
+        c0 = self.lib.odef_group_ctx(self._h, 0)
+        nb = C.c_size_t()
+        self._chk_ctx(0, self.lib.odef_field_bytes(c0, F_T, C.byref(nb)))
+        t = np.empty(nb.value // 8)
+        if nb.value == 0 or self.lib.odef_get(c0, F_T, t.ctypes.data_as(_vp), nb.value) != 0:
+            raise OdefError("data_loglik: needs a fixed-grid solve first")
+        saves, comps, values, noise, per_traj = _observation_arrays(t, self.d, self.N, times, data, noise_var, components)
+        self._obs_bufs = []
+        parts = []
+        for g in range(self.G):
+            first, count = self.shard(g)
+            vals = values[:, :, first:first + count] if per_traj else values
+            bufs = _to_device((saves, comps, vals, noise), self._devices[g])
+            self._obs_bufs.append(bufs)
+            parts.append(Context._data_loglik(self.lib, self.lib.odef_group_ctx(self._h, g), bufs))
+        return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
 
     def ensemble_moments(self, source: int):
         """Ensemble summary of the WHOLE ensemble: every shard reduces its own records on its device (`odef_summary_field`),
@@ -558,6 +640,38 @@ class Context:
         read only -- e.g. a tight solve's `odef_dense_output` on this grid.  Fixed grids only; ptr = 0 lets it go."""
         self._chk(self.lib.odef_bind_device(self._h, E_REFERENCE, _vp(ptr) if ptr else None, nbytes))
 
+    def bind_observations(self, save_ptr: int, comp_ptr: int, value_ptr: int, noise_ptr: int, M: int, o: int, per_trajectory: bool):
+        """The observations of `data_loglik`, device memory that stays the caller's (read only): save indices int64 [M],
+        components int64 [o], values double [M][o] (shared) or [M][o][N] (per trajectory), noise variances double [o]."""
+        nv = M * o * (self.N if per_trajectory else 1) * 8
+        for f, ptr, nb in ((L_OBS_SAVE, save_ptr, M * 8), (L_OBS_COMPONENT, comp_ptr, o * 8), (L_OBS_VALUE, value_ptr, nv),
+                           (L_OBS_NOISE, noise_ptr, o * 8)):
+            self._chk(self.lib.odef_bind_device(self._h, f, _vp(ptr) if ptr else None, nb))
+
+    @staticmethod
+    def _data_loglik(lib, h, bufs=None):
+        """(loglik [N], mahalanobis [N]) of the context `h`; `bufs`: torch tensors (saves, comps, values, noise) to bind first."""
+        if bufs is not None:
+            for f, b in zip((L_OBS_SAVE, L_OBS_COMPONENT, L_OBS_VALUE, L_OBS_NOISE), bufs):
+                if lib.odef_bind_device(h, f, _vp(b.data_ptr()), b.numel() * 8) != 0:
+                    raise OdefError(lib.odef_last_error(h).decode())
+        out = []
+        for f in (L_DATA_LOGLIK, L_DATA_MAHALANOBIS):
+            b = C.c_size_t()
+            if lib.odef_field_bytes(h, f, C.byref(b)) != 0:
+                raise OdefError(lib.odef_last_error(h).decode())
+            a = np.empty(b.value // 8)
+            if lib.odef_get(h, f, a.ctypes.data_as(_vp), b.value) != 0:
+                raise OdefError(lib.odef_last_error(h).decode())
+            out.append(a)
+        return tuple(out)
+
+    def data_loglik(self):
+        """Per-trajectory log-likelihood of the bound observations under the posterior of the last fixed-grid solve, and the
+        Mahalanobis sum (chi^2 with M o degrees of freedom for a calibrated model), reduced on the device (`odef_data_field`):
+        (loglik [N], mahalanobis [N]).  The first request after the records or the observations changed launches the pass."""
+        return self._data_loglik(self.lib, self._h)
+
     def device_ptr(self, f: int):
         p, b = _vp(), C.c_size_t()
         self._chk(self.lib.odef_get_device(self._h, f, C.byref(p), C.byref(b)))
@@ -567,8 +681,8 @@ class Context:
         self._chk(self.lib.odef_bind_device(self._h, f, _vp(ptr), nbytes))
 
     def kernel_name(self, which=0) -> str:
-        """Name of the kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) pass launched, as a
-        profiler prints it."""
+        """Name of the kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) / data-likelihood
+        (4) pass launched, as a profiler prints it."""
         buf = C.create_string_buffer(256)
         self._chk(self.lib.odef_kernel_name(self._h, which, buf, 256))
         return buf.value.decode()
@@ -1004,6 +1118,21 @@ class EnsembleSolution:
                 a = None
             self._cache["u_analytic"] = a
         return self._cache["u_analytic"]
+
+    def data_loglik(self, times, data, noise_var, components=None):
+        """Log-likelihood of noisy observations of the solution per trajectory, on the device: for y_j = u(times[j])[components] +
+        N(0, diag noise_var), the marginal likelihood under the Gauss-Markov posterior the filter records and the smoother's
+        backward transitions define (Tronarp, Bosch, Hennig 2022; later versions of the reference: `fenrir_data_loglik`).
+        `times` must equal entries of `sol.t` exactly; `data` is [M, o] (shared) or [N, M, o]; `noise_var` a scalar or [o];
+        `components` defaults to all d.  Returns (loglik [N], mahalanobis [N]): with per-trajectory u0 or p, argmax of the first
+        is the candidate that explains the data best; the second is chi^2 with M o degrees of freedom for a calibrated model.
+        Fixed grids only."""
+        if self.adaptive:
+            raise OdefError("data_loglik: observation times are per ensemble, the grid of an adaptive solve is per trajectory; "
+                            "solve on a fixed grid that contains the observation times")
+        arrays = _observation_arrays(self.t, self.d, self.ctx.N, times, data, noise_var, components)
+        self._obs_bufs = _to_device(arrays[:4], self.ctx.cfg.device)  # device memory owned by torch, kept alive by the solution
+        return Context._data_loglik(self.ctx.lib, self.ctx._h, self._obs_bufs)
 
     def summary(self, t=None, smoothed: Optional[bool] = None) -> EnsembleSummary:
         """Mean path of the ensemble and its uncertainty, reduced on the device (`odef_summary_field`): nothing but the four
