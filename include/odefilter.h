@@ -142,6 +142,28 @@ typedef enum {
   ODEF_F_COUNT_
 } odef_field;
 
+/* Derived outputs and their caches.  Three families of fields are computed from the records on the device when first asked for --
+ * the ensemble summary (odef_summary_field), the solution errors (odef_errors_field) and the data log-likelihood
+ * (odef_data_field) -- and cached; odef_field_bytes, odef_get and odef_get_device serve them like any other field.  One rule says
+ * when a cached result is dropped, so that the next request computes it again.  The context tracks six things that can change:
+ *   the filter records    MEAN, COV_TRIL, DIFFUSION, T                 source 0
+ *   the smoothed records  SMOOTH_MEAN, SMOOTH_COV_TRIL                 source 1
+ *   the dense records     DENSE_MEAN, DENSE_COV_TRIL                   source 2
+ *   the problem           u0, p, t0
+ *   the bound truth       ODEF_E_REFERENCE
+ *   the observations      ODEF_L_OBS_SAVE / COMPONENT / VALUE / NOISE
+ * and what is derived from what:
+ *   the summary of source k       its record set; a new problem drops it as well
+ *   the errors of source k        its record set, the bound truth, the problem
+ *   the data log-likelihood       the filter records, the observations, the problem
+ *   the filter records that odef_solve_fixed leaves staged for odef_smooth (the workgroup-per-trajectory path)   the filter records
+ * A record set changes when an entry point writes it -- odef_solve_* all three (every summary includes its trajectories by the
+ * RETCODE of the solve), odef_smooth the smoothed, odef_dense_output / odef_dense_sample the dense records -- and when the caller
+ * may: odef_bind_device of one of its fields replaces the buffer, and odef_get_device of one hands out a WRITABLE pointer, so both
+ * count as a change of the whole set.  odef_set_problem* change the problem, a bind of ODEF_E_REFERENCE the truth, a bind of an
+ * ODEF_L_OBS_* the observations.  odef_get, the host copy, changes nothing.  Records edited through a pointer taken EARLIER are not
+ * seen: take the pointer again (or bind) after writing. */
+
 /* Ensemble summary per time, reduced on the device (nothing in the reference: it has no ensemble).  For one time and the n
  * trajectories that are INCLUDED there -- RETCODE == ODEF_RET_SUCCESS and the d solution entries of the mean at that time finite --
  * with mu_i the solution part of the posterior mean (rows 0..d-1 of a record) and Sigma_i the d x d solution block of its covariance:
@@ -154,8 +176,8 @@ typedef enum {
  * odef_n_save), 1: the smoothed records, 2: the last odef_dense_output / odef_dense_sample result (n_t = n_q).  odef_field_bytes,
  * odef_get and odef_get_device accept these ids (odef_bind_device does not).  The first request for a source after its records
  * changed runs the reduction on the context's stream (two passes, the covariance of the means is centred before it is squared;
- * deterministic, no floating-point atomics) and caches the four arrays; odef_solve_*, odef_smooth, odef_dense_output,
- * odef_dense_sample and odef_set_problem* invalidate them.  Refused with a message: any source before a solve, source 1 before
+ * deterministic, no floating-point atomics) and caches the four arrays (dropped as "Derived outputs and their caches" above
+ * says).  Refused with a message: any source before a solve, source 1 before
  * odef_smooth, source 2 before a dense output, sources 0 / 1 after an ADAPTIVE solve (the records of one save index lie at
  * different times per trajectory: evaluate odef_dense_output at common times and use source 2).  With ODEF_SAVE_FINAL source 0
  * summarises the one record.  odef_kernel_time_ms / odef_kernel_name report the last reduction as which = 2. */
@@ -195,8 +217,8 @@ typedef enum {
  *       only, never written, fixed grids only; (ptr = NULL lets it go).  A bound reference takes precedence; U_ANALYTIC is then
  *       that buffer.
  * The first request for a source runs the pass on the context's stream (deterministic, no floating-point atomics: two requests
- * agree bit for bit) and caches the five small arrays; odef_solve_*, odef_smooth (source 1), odef_set_problem* and the bind of
- * ODEF_E_REFERENCE invalidate them.  Refused with a message: before a solve, source 1 before odef_smooth, a field without
+ * agree bit for bit) and caches the five small arrays (dropped as "Derived outputs and their caches" above says).  Refused
+ * with a message: before a solve, source 1 before odef_smooth, a field without
  * `analytic` and nothing bound, a bound reference after an ADAPTIVE solve (per-trajectory times: use `analytic`).  A trajectory
  * whose RETCODE is not Success still gets numbers over the saves it has; non-finite entries propagate as NaN.
  * odef_kernel_time_ms / odef_kernel_name report the last pass as which = 3. */
@@ -234,9 +256,8 @@ typedef enum {
  *   ODEF_L_OBS_VALUE      double [M][o]        shared by the ensemble, or [M][o][N] per trajectory (told by the byte count, as for p)
  *   ODEF_L_OBS_NOISE      double [o]           variances r > 0, R = diag r
  * The first request runs the pass on the context's stream (one launch, one lane per trajectory; SAVE, COMPONENT and NOISE are copied
- * to the host and validated there) and caches both outputs; two requests agree bit for bit.  The cache is dropped by odef_solve_*,
- * odef_set_problem*, a bind of any of the four inputs, and a bind or odef_get_device of MEAN, COV_TRIL, DIFFUSION or T (the pointer
- * handed out is writable).  Refused with a message: before a solve; after an ADAPTIVE solve (observation times are per ensemble, the
+ * to the host and validated there) and caches both outputs (dropped as "Derived outputs and their caches" above says); two
+ * requests agree bit for bit.  Refused with a message: before a solve; after an ADAPTIVE solve (observation times are per ensemble, the
  * grid per trajectory); the MV diffusion models; a (d, q) without a kernel (built for d <= 4, q <= 5, d (q + 1) <= 20); an input
  * missing; byte counts that do not agree; saves or components that are not strictly increasing or out of range; a noise variance
  * that is not finite and positive; a context that kept only the final state.  A non-positive pivot of S or a NaN in a record the

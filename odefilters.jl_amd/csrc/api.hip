@@ -38,6 +38,9 @@ struct Buf {
 struct RhsInfo { int d, np; };
 const RhsInfo kRhs[] = {{2, 3}, {3, 3}, {2, 4}, {2, 1}, {2, 2}, {28, 0}, {16, 1}, {2, 3}};
 
+// the passes a context times and names: `which` of odef_kernel_time_ms / odef_kernel_name
+enum Pass { kPassFilter = 0, kPassSmooth = 1, kPassSummary = 2, kPassErrors = 3, kPassDataLik = 4, kPassCount };
+
 }  // namespace
 
 struct odef_ctx {
@@ -70,14 +73,14 @@ struct odef_ctx {
   const FieldLaunch* field = nullptr;  // launch functions of the vector field (compiled-in, or owned by the registry in jit.hip)
   double* d_ws = nullptr;   // per-trajectory workspace of the team kernels
   double* d_stage = nullptr;  // trajectory-major stage of the covariance records (D = 168 smoother, record_stage.h)
-  long stage_filter_recs = 0; // > 0: the last solve left this many filter records in the stage (record r at r N ld)
+  long stage_filter_recs = 0; // > 0: the stage holds this many filter records (record r at r N ld); reset by records_changed
   size_t stage_cap = 0;     // doubles
   size_t ws_cap = 0;
   Buf f[ODEF_F_COUNT_];
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-  int nl[5] = {0, 0, 0, 0, 0};
-  char kname[5][192] = {"", "", "", "", ""};  // kernel of the last filter / smoother / ensemble-summary / solution-error / data-likelihood pass (odef_kernel_name)
+  float ms[kPassCount] = {};
+  int nl[kPassCount] = {};
+  char kname[kPassCount][192] = {};  // kernel of the last pass of each kind (odef_kernel_name)
   SummaryState summary;  // cached ensemble summaries of the filter, smoothed and dense records (odef_summary_field)
   ErrorsState errors;    // cached solution errors of the filter and smoothed records (odef_errors_field)
   const double* err_ref = nullptr;  // ODEF_E_REFERENCE: the bound truth [n_save][d][N] (caller memory, read only)
@@ -253,46 +256,86 @@ int set_device(odef_ctx* c) {
   return 0;
 }
 
+// What an entry point, or a caller holding a writable pointer, may have changed.  Record set k (kFilterRecs << k) is source k of the
+// derived outputs.
+enum : unsigned {
+  kFilterRecs = 1u << 0,    // ODEF_F_MEAN, COV_TRIL, DIFFUSION, T
+  kSmoothRecs = 1u << 1,    // ODEF_F_SMOOTH_MEAN, SMOOTH_COV_TRIL
+  kDenseRecs = 1u << 2,     // ODEF_F_DENSE_MEAN, DENSE_COV_TRIL
+  kAllRecs = kFilterRecs | kSmoothRecs | kDenseRecs,
+  kProblem = 1u << 3,       // u0, p, t0
+  kTruth = 1u << 4,         // ODEF_E_REFERENCE
+  kObservations = 1u << 5,  // ODEF_L_OBS_*
+};
+
+// the record set an ODEF_F_* id belongs to (0: none)
+unsigned record_set_of(int field) {
+  switch (field) {
+    case ODEF_F_MEAN: case ODEF_F_COV_TRIL: case ODEF_F_DIFFUSION: case ODEF_F_T: return kFilterRecs;
+    case ODEF_F_SMOOTH_MEAN: case ODEF_F_SMOOTH_COV_TRIL: return kSmoothRecs;
+    case ODEF_F_DENSE_MEAN: case ODEF_F_DENSE_COV_TRIL: return kDenseRecs;
+    default: return 0;
+  }
+}
+
+// The one statement of what is computed from what (include/odefilter.h, "Derived outputs and their caches"): everything derived
+// from a member of `what` is dropped, and the next request for it runs its pass again.
+void records_changed(odef_ctx* c, unsigned what) {
+  // summary of source k: record set k -- and the problem, of which it makes no use: the records still on the device answer the
+  // problem before, and a summary asked for after odef_set_problem* has always been computed anew
+  for (int k = 0; k < 3; ++k)
+    if (what & (kFilterRecs << k | kProblem)) c->summary.src[k].valid = false;
+  for (int k = 0; k < 2; ++k)  // errors (and the analytic truth) of source k: record set k, the bound truth, the problem
+    if (what & (kFilterRecs << k | kTruth | kProblem)) c->errors.src[k].valid = c->errors.src[k].truth_valid = false;
+  // data likelihood: the filter records, the observations, the problem
+  if (what & (kFilterRecs | kObservations | kProblem)) c->datalik.valid = false;
+  // The filter records resident in the stage: the filter records.  odef_smooth works in the stage and leaves the smoothed records
+  // (or another block layout) there, so new smoothed records end the residency as well.
+  if (what & (kFilterRecs | kSmoothRecs)) c->stage_filter_recs = 0;
+}
+
+// One family of derived outputs (odef_summary_field / odef_errors_field / odef_data_field).  `check` touches no device; `fetch`
+// runs after it and returns the cached device array, running the pass first when the cache is stale.
+struct DerivedFamily {
+  bool (*owns)(int field);
+  int (*check)(const odef_ctx* c, int field, const char* who);  // 0, or -1 with the reason in odef_last_error
+  size_t (*bytes)(const odef_ctx* c, int field);
+  int (*fetch)(odef_ctx* c, int field, const char* who, void** ptr);
+};
+
 // odef_summary_field: id = ODEF_S_BASE + 8 source + quantity
 bool is_summary_field(int field) {
   return field >= ODEF_S_BASE && field < ODEF_S_BASE + 8 * 3 && (field - ODEF_S_BASE) % 8 < 4;
 }
-// (the records of `source` changed: its cached summary goes, and for the filter / smoothed records the cached solution errors)
-void invalidate_summary(odef_ctx* c, int source) {
-  c->summary.src[source].valid = false;
-  if (source < 2) c->errors.src[source].valid = c->errors.src[source].truth_valid = false;
-}
-void invalidate_summaries(odef_ctx* c) {
-  for (int k = 0; k < 3; ++k) invalidate_summary(c, k);
-  c->datalik.valid = false;  // (every caller changes the filter records or the problem)
-}
 
-// number of times of a summary source, or -1 with the reason in odef_last_error
-long summary_times(const odef_ctx* c, int source, const char* who) {
+// number of times of a summary source
+long summary_times(const odef_ctx* c, int source) { return source == 2 ? c->n_q : c->n_save; }
+
+int summary_check(const odef_ctx* c, int field, const char* who) {
+  const int source = (field - ODEF_S_BASE) / 8;
   if (!c->solved) return fail(c, "%s: ensemble summary requested before a solve (call odef_solve_* first)", who);
   if (source == 2) {
     if (!c->f[ODEF_F_DENSE_MEAN].valid || c->n_q < 1)
       return fail(c, "%s: ensemble summary of source 2 needs odef_dense_output (or odef_dense_sample) first", who);
-    return c->n_q;
+    return 0;
   }
   if (c->adaptive)
     return fail(c, "%s: the records of one save index of an adaptive solve lie at different times per trajectory; "
                    "evaluate odef_dense_output at common times and use source 2", who);
   if (source == 1 && !c->smoothed_done) return fail(c, "%s: ensemble summary of the smoothed records needs odef_smooth first", who);
-  return c->n_save;
+  return 0;
 }
 
-size_t summary_bytes(const odef_ctx* c, int quantity, long n_t) {
+size_t summary_bytes(const odef_ctx* c, int field) {
+  const int source = (field - ODEF_S_BASE) / 8, quantity = (field - ODEF_S_BASE) % 8;
   const size_t tri = (size_t)c->d * (c->d + 1) / 2;
-  return (size_t)n_t * 8 * (quantity == 0 ? 1 : quantity == 1 ? (size_t)c->d : tri);
+  return (size_t)summary_times(c, source) * 8 * (quantity == 0 ? 1 : quantity == 1 ? (size_t)c->d : tri);
 }
 
 // the cached array of a summary field; the first request after the source's records changed runs the reduction
-int summary_field(odef_ctx* c, int field, const char* who, void** ptr, size_t* bytes) {
+int summary_fetch(odef_ctx* c, int field, const char* who, void** ptr) {
   const int source = (field - ODEF_S_BASE) / 8, quantity = (field - ODEF_S_BASE) % 8;
-  const long n_t = summary_times(c, source, who);
-  if (n_t < 0) return -1;
-  if (set_device(c)) return -1;
+  const long n_t = summary_times(c, source);
   SummaryCache& sc = c->summary.src[source];
   if (!sc.valid || sc.n_t != n_t) {
     static const int kMean[3] = {ODEF_F_MEAN, ODEF_F_SMOOTH_MEAN, ODEF_F_DENSE_MEAN};
@@ -309,12 +352,12 @@ int summary_field(odef_ctx* c, int field, const char* who, void** ptr, size_t* b
     if (!a.mean || !a.cov || !a.retcode) return fail(c, "%s: the records of summary source %d hold no data", who, source);
     std::string err;
     int walk = 0;
-    if (summary_run(c->summary, sc, a, c->stream, &c->ms[2], &c->nl[2], &walk, err)) return fail(c, "%s: %s", who, err.c_str());
-    std::snprintf(c->kname[2], sizeof c->kname[2], "odef::summary_sums_kernel<%d>", walk);
+    if (summary_run(c->summary, sc, a, c->stream, &c->ms[kPassSummary], &c->nl[kPassSummary], &walk, err))
+      return fail(c, "%s: %s", who, err.c_str());
+    std::snprintf(c->kname[kPassSummary], sizeof c->kname[kPassSummary], "odef::summary_sums_kernel<%d>", walk);
   }
   void* const p[4] = {sc.count, sc.mean, sc.within, sc.between};
   *ptr = p[quantity];
-  *bytes = summary_bytes(c, quantity, n_t);
   return 0;
 }
 
@@ -323,13 +366,13 @@ bool is_errors_field(int field) {
   return field >= ODEF_E_BASE && field < ODEF_E_BASE + 8 * 2 && (field - ODEF_E_BASE) % 8 <= ODEF_E_U_ANALYTIC - ODEF_E_BASE;
 }
 
-size_t errors_bytes(const odef_ctx* c, int quantity) {
+size_t errors_bytes(const odef_ctx* c, int field) {
   const size_t N = (size_t)c->cfg.n_traj;
-  return quantity == ODEF_E_U_ANALYTIC - ODEF_E_BASE ? (size_t)c->n_save * c->d * N * sizeof(double) : N * 8;
+  return (field - ODEF_E_BASE) % 8 == ODEF_E_U_ANALYTIC - ODEF_E_BASE ? (size_t)c->n_save * c->d * N * sizeof(double) : N * 8;
 }
 
-// 0 when the solution errors of `source` can be computed, else -1 with the reason in odef_last_error (no device is touched)
-int errors_check(const odef_ctx* c, int source, const char* who) {
+int errors_check(const odef_ctx* c, int field, const char* who) {
+  const int source = (field - ODEF_E_BASE) / 8;
   if (!c->solved) return fail(c, "%s: solution errors requested before a solve (call odef_solve_* first)", who);
   if (source == 1 && !c->smoothed_done) return fail(c, "%s: solution errors of the smoothed records need odef_smooth first", who);
   if (!c->err_ref && !c->field->errors)
@@ -346,13 +389,10 @@ int errors_check(const odef_ctx* c, int source, const char* who) {
 }
 
 // the cached array of a solution-error field; the first request after the source's records (or the truth) changed runs the pass
-int errors_field(odef_ctx* c, int field, const char* who, void** ptr, size_t* bytes) {
+int errors_fetch(odef_ctx* c, int field, const char* who, void** ptr) {
   const int source = (field - ODEF_E_BASE) / 8, quantity = (field - ODEF_E_BASE) % 8;
-  if (errors_check(c, source, who)) return -1;
-  if (set_device(c)) return -1;
   ErrorsCache& ec = c->errors.src[source];
   const bool truth = quantity == ODEF_E_U_ANALYTIC - ODEF_E_BASE;
-  *bytes = errors_bytes(c, quantity);
   if (truth && c->err_ref) {  // the truth is the caller's own buffer
     *ptr = const_cast<double*>(c->err_ref);
     return 0;
@@ -387,7 +427,8 @@ int errors_field(odef_ctx* c, int field, const char* who, void** ptr, size_t* by
     if (!r.mean || !r.cov) return fail(c, "%s: the records of source %d hold no data", who, source);
     std::string err;
     const int rc = truth ? errors_truth(ec, r, c->stream, err)
-                         : errors_run(c->errors, ec, r, c->stream, &c->ms[3], &c->nl[3], c->kname[3], sizeof c->kname[3], err);
+                         : errors_run(c->errors, ec, r, c->stream, &c->ms[kPassErrors], &c->nl[kPassErrors], c->kname[kPassErrors],
+                                      sizeof c->kname[kPassErrors], err);
     if (rc) return fail(c, "%s: %s", who, err.c_str());
   }
   *ptr = truth ? (void*)ec.truth : quantity == ODEF_E_NUSED - ODEF_E_BASE ? (void*)ec.nused : (void*)ec.val[quantity];
@@ -397,13 +438,8 @@ int errors_field(odef_ctx* c, int field, const char* who, void** ptr, size_t* by
 // odef_data_field: the two outputs, and the four inputs that odef_bind_device alone takes
 bool is_datalik_output(int field) { return field == ODEF_L_DATA_LOGLIK || field == ODEF_L_DATA_MAHALANOBIS; }
 bool is_datalik_input(int field) { return field >= ODEF_L_OBS_SAVE && field <= ODEF_L_OBS_NOISE; }
-// the records the pass reads: a caller that binds them, or takes their (writable) device pointer, may change them
-bool is_datalik_record(int field) {
-  return field == ODEF_F_MEAN || field == ODEF_F_COV_TRIL || field == ODEF_F_DIFFUSION || field == ODEF_F_T;
-}
 
-// 0 when the data log-likelihood can be computed, else -1 with the reason in odef_last_error (no device is touched)
-int datalik_check(const odef_ctx* c, const char* who) {
+int datalik_check(const odef_ctx* c, int, const char* who) {
   if (!c->solved) return fail(c, "%s: data log-likelihood requested before a solve (call odef_solve_* first)", who);
   if (c->adaptive)
     return fail(c, "%s: data log-likelihood after an adaptive solve: the observation times are per ensemble, the grid of an adaptive "
@@ -422,9 +458,9 @@ int datalik_check(const odef_ctx* c, const char* who) {
 }
 
 // the cached array of a data log-likelihood field; the first request after the records or an input changed runs the pass
-int datalik_field(odef_ctx* c, int field, const char* who, void** ptr, size_t* bytes) {
-  if (datalik_check(c, who)) return -1;
-  if (set_device(c)) return -1;
+size_t datalik_bytes(const odef_ctx* c, int) { return (size_t)c->cfg.n_traj * sizeof(double); }
+
+int datalik_fetch(odef_ctx* c, int field, const char* who, void** ptr) {
   if (!c->datalik.valid) {
     DataLikRequest r;
     std::memset(&r, 0, sizeof r);
@@ -449,11 +485,31 @@ int datalik_field(odef_ctx* c, int field, const char* who, void** ptr, size_t* b
     r.val_bytes = c->obs[2].bytes;
     r.noise_bytes = c->obs[3].bytes;
     std::string err;
-    if (datalik_run(c->datalik, r, c->stream, &c->ms[4], &c->nl[4], c->kname[4], sizeof c->kname[4], err))
+    if (datalik_run(c->datalik, r, c->stream, &c->ms[kPassDataLik], &c->nl[kPassDataLik], c->kname[kPassDataLik],
+                    sizeof c->kname[kPassDataLik], err))
       return fail(c, "%s: %s", who, err.c_str());
   }
   *ptr = c->datalik.out[field - ODEF_L_BASE];
-  *bytes = (size_t)c->cfg.n_traj * sizeof(double);
+  return 0;
+}
+
+const DerivedFamily kDerived[] = {
+    {is_summary_field, summary_check, summary_bytes, summary_fetch},
+    {is_errors_field, errors_check, errors_bytes, errors_fetch},
+    {is_datalik_output, datalik_check, datalik_bytes, datalik_fetch},
+};
+
+// the family that owns a field id, or nullptr: an ODEF_F_* buffer, a bind-only id, or no id at all
+const DerivedFamily* derived_family(int field) {
+  for (const DerivedFamily& fam : kDerived)
+    if (fam.owns(field)) return &fam;
+  return nullptr;
+}
+
+// the device array and byte count of a derived field
+int derived_fetch(odef_ctx* c, const DerivedFamily* fam, int field, const char* who, void** ptr, size_t* bytes) {
+  if (fam->check(c, field, who) || set_device(c) || fam->fetch(c, field, who, ptr)) return -1;
+  *bytes = fam->bytes(c, field);
   return 0;
 }
 
@@ -662,15 +718,7 @@ void odef_destroy(odef_ctx* c) {
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
   for (int k = 0; k < ODEF_F_COUNT_; ++k)
     if (k != ODEF_F_U0 && c->f[k].owned && c->f[k].ptr) (void)hipFree(c->f[k].ptr);
-  if (c->d_u0) (void)hipFree(c->d_u0);
-  if (c->d_p) (void)hipFree(c->d_p);
-  if (c->d_ws) (void)hipFree(c->d_ws);
-  if (c->d_stage) (void)hipFree(c->d_stage);
-  if (c->d_hs) (void)hipFree(c->d_hs);
-  if (c->d_ptab) (void)hipFree(c->d_ptab);
-  if (c->d_tgrid) (void)hipFree(c->d_tgrid);
-  if (c->d_tq) (void)hipFree(c->d_tq);
-  if (c->d_tab_idx) (void)hipFree(c->d_tab_idx);
+  free_device(c->d_u0, c->d_p, c->d_ws, c->d_stage, c->d_hs, c->d_ptab, c->d_tgrid, c->d_tq, c->d_tab_idx);
   summary_free(c->summary);
   errors_free(c->errors);
   datalik_free(c->datalik);
@@ -711,7 +759,7 @@ int odef_set_problem(odef_ctx* c, const double* u0, const double* p, double t0) 
   c->t0 = t0;
   c->have_problem = true;
   clear_lin(c);
-  invalidate_summaries(c);
+  records_changed(c, kProblem);
   return 0;
 }
 
@@ -726,7 +774,7 @@ int odef_set_problem_device(odef_ctx* c, const double* d_u0, const double* d_p, 
   c->t0 = t0;
   c->have_problem = true;
   clear_lin(c);
-  invalidate_summaries(c);
+  records_changed(c, kProblem);
   return 0;
 }
 
@@ -748,11 +796,16 @@ int odef_set_problem_perturbed(odef_ctx* c, const double* base_u0, const double*
   c->t0 = t0;
   c->have_problem = true;
   clear_lin(c);
-  invalidate_summaries(c);
+  records_changed(c, kProblem);
   return 0;
 }
 
+// the buffers of a new solve
 static int alloc_outputs(odef_ctx* c, long n_save) {
+  // The solve rewrites the filter records and RETCODE, by which every summary source includes its trajectories; the smoothed
+  // records belong to the solve before.  Said before the launch: a solve that fails half way leaves no cache of the old records
+  // behind, and the launch is then free to note the records it leaves in the stage (FieldLaunch::filter).
+  records_changed(c, kAllRecs);
   static const int per_save[] = {ODEF_F_MEAN, ODEF_F_COV_TRIL, ODEF_F_DIFFUSION};
   for (int f : per_save)
     if (ensure(c, f, field_count(c, f, n_save) * sizeof(double))) return -1;
@@ -793,10 +846,10 @@ static void fill_params(odef_ctx* c, FilterParams& P) {
 static int complete_pending(odef_ctx* c) {
   if (c->pending == 1) {
     HIPCHK(c, hipEventSynchronize(c->ev[1]));
-    HIPCHK(c, hipEventElapsedTime(&c->ms[0], c->ev[0], c->ev[1]));
+    HIPCHK(c, hipEventElapsedTime(&c->ms[kPassFilter], c->ev[0], c->ev[1]));
   } else if (c->pending == 2) {
     HIPCHK(c, hipEventSynchronize(c->ev[3]));
-    HIPCHK(c, hipEventElapsedTime(&c->ms[1], c->ev[2], c->ev[3]));
+    HIPCHK(c, hipEventElapsedTime(&c->ms[kPassSmooth], c->ev[2], c->ev[3]));
   }
   c->pending = 0;
   return 0;
@@ -811,7 +864,7 @@ static int finish_filter(odef_ctx* c, int nlaunch) {
                        (double*)c->f[ODEF_F_LOGLIK].ptr, c->adaptive ? (const int*)c->f[ODEF_F_NSAVED].ptr : (const int*)nullptr,
                        N, c->n_save, c->d, c->D);
     ++nlaunch;
-    c->stage_filter_recs = 0;
+    records_changed(c, kFilterRecs);
   } else if (c->cfg.diffusion != ODEF_DIFFUSION_DYNAMIC && c->cfg.diffusion != ODEF_DIFFUSION_DYNAMIC_MV) {
     const long N = c->cfg.n_traj;
     hipLaunchKernelGGL(scale_cov_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, c->stream,
@@ -819,14 +872,13 @@ static int finish_filter(odef_ctx* c, int nlaunch) {
                        (double*)c->f[ODEF_F_LOGLIK].ptr, c->adaptive ? (const int*)c->f[ODEF_F_NSAVED].ptr : (const int*)nullptr,
                        N, c->n_save, c->TRI);
     ++nlaunch;
-    c->stage_filter_recs = 0;  // (records the filter may have left in the stage are the unscaled ones)
+    records_changed(c, kFilterRecs);  // (records the filter may have left in the stage are the unscaled ones)
   }
   HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
   HIPCHK(c, hipGetLastError());
-  c->nl[0] = nlaunch;
+  c->nl[kPassFilter] = nlaunch;
   c->solved = true;
   c->smoothed_done = false;
-  invalidate_summaries(c);
   c->pending = 1;
   return c->defer ? 0 : complete_pending(c);
 }
@@ -934,7 +986,7 @@ int odef_solve_fixed(odef_ctx* c, const double* tgrid, int64_t n_t) {
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
   const int rc = c->field->filter(c->q, is_ek1(c->cfg.alg), P, c->stream, 0, have ? c->d_stage : nullptr, have, &c->stage_filter_recs);
   if (rc) return fail(c, "odef_solve_fixed: no %skernel for rhs %d order %d", lin ? "IEKS " : "", c->cfg.rhs_id, c->q);
-  std::snprintf(c->kname[0], sizeof c->kname[0], "%s", last_kernel());
+  std::snprintf(c->kname[kPassFilter], sizeof c->kname[kPassFilter], "%s", last_kernel());
   return finish_filter(c, 1);
 }
 
@@ -973,7 +1025,7 @@ int odef_solve_adaptive(odef_ctx* c, double t1, double abstol, double reltol, do
   HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
   const int rc = c->field->filter(c->q, is_ek1(c->cfg.alg), P, c->stream, 1, nullptr, 0, &c->stage_filter_recs);
   if (rc) return fail(c, "odef_solve_adaptive: no kernel for rhs %d order %d", c->cfg.rhs_id, c->q);
-  std::snprintf(c->kname[0], sizeof c->kname[0], "%s", last_kernel());
+  std::snprintf(c->kname[kPassFilter], sizeof c->kname[kPassFilter], "%s", last_kernel());
   return finish_filter(c, 1);
 }
 
@@ -1025,11 +1077,11 @@ int odef_smooth(odef_ctx* c) {
     const bool resident = !S.adaptive && n_rec >= 3 && c->stage_filter_recs == n_rec && c->stage_cap >= (size_t)n_rec * per_rec;
     const size_t have = n_rec < 3 ? 0 : resident ? (size_t)(n_rec - 1) * per_rec : ensure_stage(c, n_rec - 1, per_rec);
     if (have) rc = c->field->smooth_staged(c->q, S, n_rec, c->d_ws, c->d_stage, have, c->stream, resident ? n_rec : 0);
-    c->stage_filter_recs = 0;  // (smoothed records now, or another block layout)
   }
   if (rc == -4) rc = c->field->smooth(c->q, S, c->d_ws, c->stream);
+  records_changed(c, kSmoothRecs);  // (whatever the launch did: the stage no longer holds the filter records either)
   if (rc) return fail(c, "odef_smooth: no kernel for d %d order %d", c->d, c->q);
-  std::snprintf(c->kname[1], sizeof c->kname[1], "%s", last_kernel());
+  std::snprintf(c->kname[kPassSmooth], sizeof c->kname[kPassSmooth], "%s", last_kernel());
   HIPCHK(c, hipEventRecord(c->ev[3], c->stream));
   HIPCHK(c, hipGetLastError());
   if (c->cfg.alg == ODEF_IEKS && !c->adaptive) {
@@ -1044,9 +1096,8 @@ int odef_smooth(odef_ctx* c) {
     c->lin_set = true;
     c->lin_grid = c->tgrid;
   }
-  c->nl[1] = 1;
+  c->nl[kPassSmooth] = 1;
   c->smoothed_done = true;
-  invalidate_summary(c, 1);
   c->pending = 2;
   return c->defer ? 0 : complete_pending(c);
 }
@@ -1068,7 +1119,7 @@ int odef_dense_output(odef_ctx* c, const double* tq, int64_t n_q, int smoothed) 
   HIPCHK(c, hipMemcpyAsync(c->d_tq, tq, sizeof(double) * n_q, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   c->n_q = (long)n_q;
-  invalidate_summary(c, 2);
+  records_changed(c, kDenseRecs);
   const size_t N = (size_t)c->cfg.n_traj;
   if (ensure(c, ODEF_F_DENSE_MEAN, (size_t)n_q * c->D * N * sizeof(double))) return -1;
   if (ensure(c, ODEF_F_DENSE_COV_TRIL, (size_t)n_q * c->TRI * N * sizeof(double))) return -1;
@@ -1163,23 +1214,13 @@ int odef_dense_sample(odef_ctx* c, const double* tq, int64_t n_q, int64_t n_samp
 int64_t odef_n_save(const odef_ctx* c) { return c ? c->n_save : -1; }
 
 int odef_field_bytes(const odef_ctx* c, int field, size_t* bytes) {
-  if (c && bytes && is_summary_field(field)) {
-    const long n_t = summary_times(c, (field - ODEF_S_BASE) / 8, "odef_field_bytes");
-    if (n_t < 0) return -1;
-    *bytes = summary_bytes(c, (field - ODEF_S_BASE) % 8, n_t);
+  if (!c || !bytes) return -1;
+  if (const DerivedFamily* fam = derived_family(field)) {
+    if (fam->check(c, field, "odef_field_bytes")) return -1;
+    *bytes = fam->bytes(c, field);
     return 0;
   }
-  if (c && bytes && is_errors_field(field)) {
-    if (errors_check(c, (field - ODEF_E_BASE) / 8, "odef_field_bytes")) return -1;
-    *bytes = errors_bytes(c, (field - ODEF_E_BASE) % 8);
-    return 0;
-  }
-  if (c && bytes && is_datalik_output(field)) {
-    if (datalik_check(c, "odef_field_bytes")) return -1;
-    *bytes = (size_t)c->cfg.n_traj * sizeof(double);
-    return 0;
-  }
-  if (!c || !bytes || field < 0 || field >= ODEF_F_COUNT_) return -1;
+  if (field < 0 || field >= ODEF_F_COUNT_) return -1;
   if (field == ODEF_F_T && !c->adaptive) { *bytes = c->tgrid.size() ? (size_t)c->n_save * sizeof(double) : 0; return 0; }
   *bytes = c->f[field].valid;
   return 0;
@@ -1187,49 +1228,37 @@ int odef_field_bytes(const odef_ctx* c, int field, size_t* bytes) {
 
 int odef_get(odef_ctx* c, int field, void* host_dst, size_t bytes) {
   if (!c || !host_dst) return fail(c, "odef_get: null argument");
-  if (is_summary_field(field)) {
-    void* src = nullptr;
-    size_t have = 0;
-    if (summary_field(c, field, "odef_get", &src, &have)) return -1;
-    if (bytes != have) return fail(c, "odef_get: field %d holds %zu bytes, caller asked for %zu", field, have, bytes);
-    HIPCHK(c, hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
+  void* src = nullptr;
+  size_t have = 0;
+  if (const DerivedFamily* fam = derived_family(field)) {
+    if (derived_fetch(c, fam, field, "odef_get", &src, &have)) return -1;
+  } else {
+    if (field < 0 || field >= ODEF_F_COUNT_) return fail(c, "odef_get: unknown field %d", field);
+    if (set_device(c)) return -1;
+    if (field == ODEF_F_T && !c->adaptive) {  // the shared grid lives on the host
+      if (c->tgrid.empty()) return fail(c, "odef_get: no solve yet");
+      const size_t need = (size_t)c->n_save * sizeof(double);
+      if (bytes != need) return fail(c, "odef_get: field T holds %zu bytes, caller asked for %zu", need, bytes);
+      if (c->n_save == 1) ((double*)host_dst)[0] = c->tgrid.back();
+      else std::memcpy(host_dst, c->tgrid.data(), need);
+      return 0;
+    }
+    const Buf& b = c->f[field];
+    if (!b.ptr || !b.valid) return fail(c, "odef_get: field %d holds no data yet", field);
+    src = b.ptr;
+    have = b.valid;
   }
-  if (is_errors_field(field) || is_datalik_output(field)) {
-    void* src = nullptr;
-    size_t have = 0;
-    if (is_datalik_output(field) ? datalik_field(c, field, "odef_get", &src, &have) : errors_field(c, field, "odef_get", &src, &have)) return -1;
-    if (bytes != have) return fail(c, "odef_get: field %d holds %zu bytes, caller asked for %zu", field, have, bytes);
-    HIPCHK(c, hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return 0;
-  }
-  if (field < 0 || field >= ODEF_F_COUNT_) return fail(c, "odef_get: unknown field %d", field);
-  if (set_device(c)) return -1;
-  if (field == ODEF_F_T && !c->adaptive) {
-    if (c->tgrid.empty()) return fail(c, "odef_get: no solve yet");
-    const size_t need = (size_t)c->n_save * sizeof(double);
-    if (bytes != need) return fail(c, "odef_get: field T holds %zu bytes, caller asked for %zu", need, bytes);
-    if (c->n_save == 1) ((double*)host_dst)[0] = c->tgrid.back();
-    else std::memcpy(host_dst, c->tgrid.data(), need);
-    return 0;
-  }
-  const Buf& b = c->f[field];
-  if (!b.ptr || !b.valid) return fail(c, "odef_get: field %d holds no data yet", field);
-  if (bytes != b.valid) return fail(c, "odef_get: field %d holds %zu bytes, caller asked for %zu", field, b.valid, bytes);
-  HIPCHK(c, hipMemcpyAsync(host_dst, b.ptr, bytes, hipMemcpyDeviceToHost, c->stream));
+  if (bytes != have) return fail(c, "odef_get: field %d holds %zu bytes, caller asked for %zu", field, have, bytes);
+  HIPCHK(c, hipMemcpyAsync(host_dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 
 int odef_get_device(odef_ctx* c, int field, void** dev_ptr, size_t* bytes) {
   if (!c || !dev_ptr || !bytes) return fail(c, "odef_get_device: null argument");
-  if (is_summary_field(field)) return summary_field(c, field, "odef_get_device", dev_ptr, bytes);
-  if (is_errors_field(field)) return errors_field(c, field, "odef_get_device", dev_ptr, bytes);
-  if (is_datalik_output(field)) return datalik_field(c, field, "odef_get_device", dev_ptr, bytes);
-  if (is_datalik_record(field)) c->datalik.valid = false;  // the pointer handed out is writable
+  if (const DerivedFamily* fam = derived_family(field)) return derived_fetch(c, fam, field, "odef_get_device", dev_ptr, bytes);
   if (field < 0 || field >= ODEF_F_COUNT_) return fail(c, "odef_get_device: unknown field %d", field);
+  records_changed(c, record_set_of(field));  // the pointer handed out is writable
   const Buf& b = c->f[field];
   if (!b.ptr || !b.valid) return fail(c, "odef_get_device: field %d holds no data yet", field);
   *dev_ptr = b.ptr;
@@ -1242,7 +1271,7 @@ int odef_bind_device(odef_ctx* c, int field, void* dev_ptr, size_t bytes) {
   if (field == ODEF_E_REFERENCE) {  // the truth of the solution errors: caller memory, read only; NULL lets it go
     c->err_ref = (const double*)dev_ptr;
     c->err_ref_bytes = dev_ptr ? bytes : 0;
-    for (int k = 0; k < 2; ++k) c->errors.src[k].valid = false;
+    records_changed(c, kTruth);
     return 0;
   }
   if (is_datalik_input(field)) {  // the observations of the data log-likelihood: caller memory, read only; NULL lets it go
@@ -1253,11 +1282,11 @@ int odef_bind_device(odef_ctx* c, int field, void* dev_ptr, size_t bytes) {
       b.bytes = bytes;
       b.bound = true;
     }
-    c->datalik.valid = false;
+    records_changed(c, kObservations);
     return 0;
   }
   if (field < 0 || field >= ODEF_F_COUNT_ || field == ODEF_F_U0) return fail(c, "odef_bind_device: field %d cannot be bound", field);
-  if (is_datalik_record(field)) c->datalik.valid = false;
+  records_changed(c, record_set_of(field));
   if (field == ODEF_F_LINEARIZE_AT && dev_ptr && c->cfg.alg != ODEF_IEKS)
     return fail(c, "odef_bind_device: ODEF_F_LINEARIZE_AT belongs to an IEKS context (alg = ODEF_IEKS)");
   if (set_device(c)) return -1;
@@ -1284,13 +1313,13 @@ int odef_synchronize(odef_ctx* c) {
 }
 
 int odef_kernel_name(odef_ctx* c, int which, char* buf, size_t n) {
-  if (!c || which < 0 || which > 4 || !buf || n == 0) return -1;
+  if (!c || which < 0 || which >= kPassCount || !buf || n == 0) return -1;
   std::snprintf(buf, n, "%s", c->kname[which]);
   return 0;
 }
 
 int odef_kernel_time_ms(odef_ctx* c, int which, float* ms, int* n_launches) {
-  if (!c || which < 0 || which > 4 || !ms) return -1;
+  if (!c || which < 0 || which >= kPassCount || !ms) return -1;
   *ms = c->ms[which];
   if (n_launches) *n_launches = c->nl[which];
   return 0;

@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <string>
 
+#include "pass_host.h"
+
 namespace odef {
 
 struct PriorConsts;  // ek_math.h
@@ -16,7 +18,7 @@ struct PriorConsts;  // ek_math.h
 struct DataLikState {
   double* out[2] = {nullptr, nullptr};  // DATA_LOGLIK, DATA_MAHALANOBIS [N], device memory owned by the context
   bool valid = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  PassTimer timer;
 };
 
 struct DataLikRequest {

@@ -42,76 +42,44 @@ bool datalik_has(int d, int q) { return d >= 1 && d <= kDataLikMaxD && q >= 1 &&
 int datalik_run(DataLikState& st, const DataLikRequest& r, hipStream_t stream, float* ms, int* n_launches, char* kname, size_t kname_n,
                 std::string& err) {
   st.valid = false;
-  char msg[256];
-  if (!datalik_has(r.d, r.q)) {
-    std::snprintf(msg, sizeof msg, "data log-likelihood: no kernel for (d, q) = (%d, %d)", r.d, r.q);
-    err = msg;
-    return -1;
-  }
+  if (!datalik_has(r.d, r.q)) return pass_fail(err, "data log-likelihood: no kernel for (d, q) = (%d, %d)", r.d, r.q);
   const int D = r.d * (r.q + 1), TRI = D * (D + 1) / 2;
-  if (r.N < 1 || r.n_save < 2 || (size_t)TRI * (size_t)r.N * sizeof(double) >= (1ull << 31)) {
-    err = "data log-likelihood: n_traj * D(D+1)/2 * 8 bytes must stay below 2 GiB per save slot; shard the ensemble";
-    return -1;
-  }
+  if (r.N < 1 || r.n_save < 2 || (size_t)TRI * (size_t)r.N * sizeof(double) >= (1ull << 31))
+    return pass_fail(err, "data log-likelihood: n_traj * D(D+1)/2 * 8 bytes must stay below 2 GiB per save slot; shard the ensemble");
   // M and o follow from the byte counts
   if (r.save_bytes == 0 || r.save_bytes % 8 || r.comp_bytes == 0 || r.comp_bytes % 8 || r.comp_bytes / 8 > (size_t)r.d ||
-      r.save_bytes / 8 > (size_t)r.n_save) {
-    std::snprintf(msg, sizeof msg,
-                  "data log-likelihood: byte counts do not agree: ODEF_L_OBS_SAVE holds %zu bytes (1 .. n_save int64), "
-                  "ODEF_L_OBS_COMPONENT %zu (1 .. d int64)", r.save_bytes, r.comp_bytes);
-    err = msg;
-    return -1;
-  }
+      r.save_bytes / 8 > (size_t)r.n_save)
+    return pass_fail(err, "data log-likelihood: byte counts do not agree: ODEF_L_OBS_SAVE holds %zu bytes (1 .. n_save int64), "
+                          "ODEF_L_OBS_COMPONENT %zu (1 .. d int64)", r.save_bytes, r.comp_bytes);
   const size_t M = r.save_bytes / 8, o = r.comp_bytes / 8;
-  if (r.noise_bytes != o * 8 || (r.val_bytes != M * o * 8 && r.val_bytes != M * o * (size_t)r.N * 8)) {
-    std::snprintf(msg, sizeof msg,
-                  "data log-likelihood: byte counts do not agree: M = %zu saves and o = %zu components need ODEF_L_OBS_NOISE of %zu bytes "
-                  "(got %zu) and ODEF_L_OBS_VALUE of %zu (shared) or %zu (per trajectory) bytes (got %zu)",
-                  M, o, o * 8, r.noise_bytes, M * o * 8, M * o * (size_t)r.N * 8, r.val_bytes);
-    err = msg;
-    return -1;
-  }
+  if (r.noise_bytes != o * 8 || (r.val_bytes != M * o * 8 && r.val_bytes != M * o * (size_t)r.N * 8))
+    return pass_fail(err,
+                     "data log-likelihood: byte counts do not agree: M = %zu saves and o = %zu components need ODEF_L_OBS_NOISE of %zu bytes "
+                     "(got %zu) and ODEF_L_OBS_VALUE of %zu (shared) or %zu (per trajectory) bytes (got %zu)",
+                     M, o, o * 8, r.noise_bytes, M * o * 8, M * o * (size_t)r.N * 8, r.val_bytes);
   std::vector<long long> idx(M + o);
   std::vector<double> noise(o);
   hipError_t e = hipMemcpyAsync(idx.data(), r.obs_save, M * 8, hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipMemcpyAsync(idx.data() + M, r.obs_comp, o * 8, hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipMemcpyAsync(noise.data(), r.obs_noise, o * 8, hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) {
-    err = std::string("data log-likelihood: ") + hipGetErrorString(e);
-    return -1;
-  }
+  if (e != hipSuccess) return pass_fail(err, "data log-likelihood: %s", hipGetErrorString(e));
   for (size_t j = 0; j < M; ++j)
-    if (idx[j] < 0 || idx[j] >= r.n_save || (j > 0 && idx[j] <= idx[j - 1])) {
-      std::snprintf(msg, sizeof msg, "data log-likelihood: observed saves must be strictly increasing within 0 .. n_save - 1 = %ld "
-                                     "(entry %zu is %lld)", r.n_save - 1, j, idx[j]);
-      err = msg;
-      return -1;
-    }
+    if (idx[j] < 0 || idx[j] >= r.n_save || (j > 0 && idx[j] <= idx[j - 1]))
+      return pass_fail(err, "data log-likelihood: observed saves must be strictly increasing within 0 .. n_save - 1 = %ld "
+                            "(entry %zu is %lld)", r.n_save - 1, j, idx[j]);
   for (size_t a = 0; a < o; ++a)
-    if (idx[M + a] < 0 || idx[M + a] >= r.d || (a > 0 && idx[M + a] <= idx[M + a - 1])) {
-      std::snprintf(msg, sizeof msg, "data log-likelihood: observed components must be strictly increasing within 0 .. d - 1 = %d "
-                                     "(entry %zu is %lld)", r.d - 1, a, idx[M + a]);
-      err = msg;
-      return -1;
-    }
+    if (idx[M + a] < 0 || idx[M + a] >= r.d || (a > 0 && idx[M + a] <= idx[M + a - 1]))
+      return pass_fail(err, "data log-likelihood: observed components must be strictly increasing within 0 .. d - 1 = %d "
+                            "(entry %zu is %lld)", r.d - 1, a, idx[M + a]);
   for (size_t a = 0; a < o; ++a)
-    if (!std::isfinite(noise[a]) || !(noise[a] > 0.0)) {
-      std::snprintf(msg, sizeof msg, "data log-likelihood: noise variances must be finite and positive (entry %zu is %g)", a, noise[a]);
-      err = msg;
-      return -1;
-    }
+    if (!std::isfinite(noise[a]) || !(noise[a] > 0.0))
+      return pass_fail(err, "data log-likelihood: noise variances must be finite and positive (entry %zu is %g)", a, noise[a]);
   for (double*& v : st.out)
     if (!v && hipMalloc((void**)&v, sizeof(double) * r.N) != hipSuccess) {
       (void)hipGetLastError();
       v = nullptr;
-      err = "data log-likelihood: out of device memory";
-      return -1;
-    }
-  for (hipEvent_t& ev : st.ev)
-    if (!ev && hipEventCreate(&ev) != hipSuccess) {
-      err = "data log-likelihood: hipEventCreate failed";
-      return -1;
+      return pass_fail(err, "data log-likelihood: out of device memory");
     }
   DataLikArgs a;
   a.pc = *r.pc;
@@ -132,7 +100,7 @@ int datalik_run(DataLikState& st, const DataLikRequest& r, hipStream_t stream, f
   a.per_traj = r.val_bytes != M * o * 8;
   a.loglik = st.out[0];
   a.maha = st.out[1];
-  (void)hipEventRecord(st.ev[0], stream);
+  if (st.timer.begin(stream) != hipSuccess) return pass_fail(err, "data log-likelihood: hipEventCreate failed");
   bool ok = false;
   switch (r.d) {
     case 1: ok = launch_order<1>(r.q, a, stream); break;
@@ -141,29 +109,17 @@ int datalik_run(DataLikState& st, const DataLikRequest& r, hipStream_t stream, f
     case 4: ok = launch_order<4>(r.q, a, stream); break;
     default: break;
   }
-  if (!ok) {
-    err = "data log-likelihood: no kernel";
-    return -1;
-  }
+  if (!ok) return pass_fail(err, "data log-likelihood: no kernel");
   if (kname) std::snprintf(kname, kname_n, "odef::data_loglik_kernel<%d, %d>", r.d, r.q);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipEventRecord(st.ev[1], stream);
-  if (e == hipSuccess) e = hipEventSynchronize(st.ev[1]);
-  if (e == hipSuccess && ms) e = hipEventElapsedTime(ms, st.ev[0], st.ev[1]);
-  if (e != hipSuccess) {
-    err = std::string("data log-likelihood: ") + hipGetErrorString(e);
-    return -1;
-  }
+  if (e = st.timer.end(stream, ms); e != hipSuccess) return pass_fail(err, "data log-likelihood: %s", hipGetErrorString(e));
   if (n_launches) *n_launches += 1;  // a running count: a request served from the cache leaves it unchanged
   st.valid = true;
   return 0;
 }
 
 void datalik_free(DataLikState& st) {
-  for (double* v : st.out)
-    if (v) (void)hipFree(v);
-  for (hipEvent_t& e : st.ev)
-    if (e) (void)hipEventDestroy(e);
+  free_device(st.out[0], st.out[1]);
+  st.timer.destroy();
   st = DataLikState{};
 }
 

@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <string>
 
+#include "pass_host.h"
+
 namespace odef {
 
 struct ErrArgs;       // errors_kernels.h
@@ -33,7 +35,7 @@ struct ErrorsState {
   double* part = nullptr;   // per-chunk partials [n_split][4][N]
   int* part_cnt = nullptr;  // [n_split][2][N]
   size_t part_cap = 0, cnt_cap = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  PassTimer timer;
 };
 
 struct ErrorsRequest {

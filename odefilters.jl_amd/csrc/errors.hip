@@ -21,19 +21,6 @@ void launch_buffer(const ErrArgs& a, const TruthBuffer::Args& t, unsigned grid, 
   hipLaunchKernelGGL((errors_partial_kernel<DR, TruthBuffer>), dim3(grid), dim3(block), lds, st, a, t);
 }
 
-bool grow(void** p, size_t* cap, size_t bytes) {
-  if (*cap >= bytes) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (hipMalloc(p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  *cap = bytes;
-  return true;
-}
-
 AnalyticArgs analytic_args(const ErrorsRequest& r) {
   AnalyticArgs t;
   t.u0 = r.u0;
@@ -52,14 +39,9 @@ int errors_run(ErrorsState& st, ErrorsCache& c, const ErrorsRequest& r, hipStrea
                size_t kname_n, std::string& err) {
   c.valid = false;
   const int tri = r.d * (r.d + 1) / 2;
-  if (r.d < 1 || r.d > 32 || r.d > r.D || tri > r.TRI || r.N < 1 || r.n_save < 1) {
-    err = "solution errors: built for d <= 32";
-    return -1;
-  }
-  if (!r.ref && !r.field) {
-    err = "solution errors: no truth";
-    return -1;
-  }
+  if (r.d < 1 || r.d > 32 || r.d > r.D || tri > r.TRI || r.N < 1 || r.n_save < 1)
+    return pass_fail(err, "solution errors: built for d <= 32");
+  if (!r.ref && !r.field) return pass_fail(err, "solution errors: no truth");
   ErrArgs a;
   a.mean = r.mean;
   a.cov = r.cov;
@@ -74,10 +56,7 @@ int errors_run(ErrorsState& st, ErrorsCache& c, const ErrorsRequest& r, hipStrea
   a.n_split = errors_split(r.N, r.n_save, a.lanes);
   a.chunk = (r.n_save + a.n_split - 1) / a.n_split;
   const long n_block = (r.N + a.lanes - 1) / a.lanes;
-  if (n_block * a.n_split >= (1l << 31)) {
-    err = "solution errors: more than 2^31 workgroups; shard the ensemble";
-    return -1;
-  }
+  if (n_block * a.n_split >= (1l << 31)) return pass_fail(err, "solution errors: more than 2^31 workgroups; shard the ensemble");
   const bool regs = r.d <= kErrRegD;
   const unsigned grid = (unsigned)(n_block * a.n_split), block = regs ? kErrBlock : 64;
   const size_t lds = regs ? 0 : (size_t)(tri + r.d) * a.lanes * sizeof(double);
@@ -86,23 +65,15 @@ int errors_run(ErrorsState& st, ErrorsCache& c, const ErrorsRequest& r, hipStrea
     for (double*& v : c.val) ok = ok && hipMalloc((void**)&v, sizeof(double) * r.N) == hipSuccess;
     if (!ok) {
       (void)hipGetLastError();
-      err = "solution errors: out of device memory";
-      return -1;
+      return pass_fail(err, "solution errors: out of device memory");
     }
   }
   if (!grow((void**)&st.part, &st.part_cap, sizeof(double) * (size_t)a.n_split * kErrPartRows * r.N) ||
-      !grow((void**)&st.part_cnt, &st.cnt_cap, sizeof(int) * (size_t)a.n_split * 2 * r.N)) {
-    err = "solution errors: out of device memory";
-    return -1;
-  }
+      !grow((void**)&st.part_cnt, &st.cnt_cap, sizeof(int) * (size_t)a.n_split * 2 * r.N))
+    return pass_fail(err, "solution errors: out of device memory");
   a.part = st.part;
   a.part_cnt = st.part_cnt;
-  for (hipEvent_t& e : st.ev)
-    if (!e && hipEventCreate(&e) != hipSuccess) {
-      err = "solution errors: hipEventCreate failed";
-      return -1;
-    }
-  (void)hipEventRecord(st.ev[0], stream);
+  if (st.timer.begin(stream) != hipSuccess) return pass_fail(err, "solution errors: hipEventCreate failed");
   if (r.ref) {
     const TruthBuffer::Args t{r.ref, r.N, r.d};
     switch (regs ? r.d : 0) {
@@ -118,19 +89,12 @@ int errors_run(ErrorsState& st, ErrorsCache& c, const ErrorsRequest& r, hipStrea
     }
     if (kname) std::snprintf(kname, kname_n, "odef::errors_partial_kernel<%d, odef::TruthBuffer>", regs ? r.d : 0);
   } else if (r.field(a, analytic_args(r), grid, block, lds, nullptr, stream, kname, kname_n)) {
-    err = "solution errors: the field's analytic launcher failed";
-    return -1;
+    return pass_fail(err, "solution errors: the field's analytic launcher failed");
   }
   hipLaunchKernelGGL(errors_fold_kernel<>, dim3((unsigned)((r.N + 255) / 256)), dim3(256), 0, stream, (const double*)st.part,
                      (const int*)st.part_cnt, a.n_split, r.N, r.d, c.val[0], c.val[1], c.val[2], c.val[3], c.nused);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipEventRecord(st.ev[1], stream);
-  if (e == hipSuccess) e = hipEventSynchronize(st.ev[1]);
-  if (e == hipSuccess && ms) e = hipEventElapsedTime(ms, st.ev[0], st.ev[1]);
-  if (e != hipSuccess) {
-    err = std::string("solution errors: ") + hipGetErrorString(e);
-    return -1;
-  }
+  if (const hipError_t e = st.timer.end(stream, ms); e != hipSuccess)
+    return pass_fail(err, "solution errors: %s", hipGetErrorString(e));
   if (n_launches) *n_launches = 2;
   c.valid = true;
   return 0;
@@ -138,19 +102,11 @@ int errors_run(ErrorsState& st, ErrorsCache& c, const ErrorsRequest& r, hipStrea
 
 int errors_truth(ErrorsCache& c, const ErrorsRequest& r, hipStream_t stream, std::string& err) {
   c.truth_valid = false;
-  if (!r.field) {
-    err = "solution errors: no analytic";
-    return -1;
-  }
-  if (!grow((void**)&c.truth, &c.truth_cap, sizeof(double) * (size_t)r.n_save * r.d * r.N)) {
-    err = "solution errors: out of device memory";
-    return -1;
-  }
+  if (!r.field) return pass_fail(err, "solution errors: no analytic");
+  if (!grow((void**)&c.truth, &c.truth_cap, sizeof(double) * (size_t)r.n_save * r.d * r.N))
+    return pass_fail(err, "solution errors: out of device memory");
   const long n_block = (r.N + kErrBlock - 1) / kErrBlock;
-  if (n_block * r.n_save >= (1l << 31)) {
-    err = "solution errors: more than 2^31 workgroups; shard the ensemble";
-    return -1;
-  }
+  if (n_block * r.n_save >= (1l << 31)) return pass_fail(err, "solution errors: more than 2^31 workgroups; shard the ensemble");
   ErrArgs a{};
   a.nsaved = r.nsaved;
   a.N = r.N;
@@ -159,26 +115,15 @@ int errors_truth(ErrorsCache& c, const ErrorsRequest& r, hipStream_t stream, std
   hipError_t e = hipSuccess;
   if (r.field(a, analytic_args(r), (unsigned)(n_block * r.n_save), kErrBlock, 0, c.truth, stream, nullptr, 0)) e = hipErrorLaunchFailure;
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) {
-    err = std::string("solution errors: ") + hipGetErrorString(e);
-    return -1;
-  }
+  if (e != hipSuccess) return pass_fail(err, "solution errors: %s", hipGetErrorString(e));
   c.truth_valid = true;
   return 0;
 }
 
 void errors_free(ErrorsState& st) {
-  for (ErrorsCache& c : st.src) {
-    for (double* v : c.val)
-      if (v) (void)hipFree(v);
-    if (c.nused) (void)hipFree(c.nused);
-    if (c.truth) (void)hipFree(c.truth);
-    c = ErrorsCache{};
-  }
-  if (st.part) (void)hipFree(st.part);
-  if (st.part_cnt) (void)hipFree(st.part_cnt);
-  for (hipEvent_t& e : st.ev)
-    if (e) (void)hipEventDestroy(e);
+  for (ErrorsCache& c : st.src) free_device(c.val[0], c.val[1], c.val[2], c.val[3], c.nused, c.truth);
+  free_device(st.part, st.part_cnt);
+  st.timer.destroy();
   st = ErrorsState{};
 }
 

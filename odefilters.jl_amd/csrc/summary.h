@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <string>
 
+#include "pass_host.h"
+
 namespace odef {
 
 // the four cached arrays of one source, device memory owned by the context
@@ -27,7 +29,7 @@ struct SummaryState {
   double* part = nullptr;  // per-wavefront partial sums of a pass [n_t][n_wave][d + tri(d)]
   int* part_cnt = nullptr; // per-wavefront counts [n_t][n_wave]
   size_t part_cap = 0, cnt_cap = 0;
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  PassTimer timer;
 };
 
 struct SummaryArgs {

@@ -32,70 +32,37 @@ void launch_centred(const SummaryArgs& a, int n_block, int n_wave, size_t lds, c
                      mbar, a.N, a.d, a.D, n_wave, part);
 }
 
-bool grow(void** p, size_t* cap, size_t bytes) {
-  if (*cap >= bytes) return true;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr;
-  *cap = 0;
-  if (hipMalloc(p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  *cap = bytes;
-  return true;
-}
-
 }  // namespace
 
 int summary_run(SummaryState& st, SummaryCache& c, const SummaryArgs& a, hipStream_t stream, float* ms, int* n_launches,
                 int* walk, std::string& err) {
   c.valid = false;
-  if (a.d < 1 || a.d > 32 || a.d > a.D || a.N < 1 || a.n_t < 1) {
-    err = "ensemble summary: built for d <= 32";
-    return -1;
-  }
+  if (a.d < 1 || a.d > 32 || a.d > a.D || a.N < 1 || a.n_t < 1) return pass_fail(err, "ensemble summary: built for d <= 32");
   const int tri = a.d * (a.d + 1) / 2, R = a.d + tri;
-  if (tri > a.TRI) {
-    err = "ensemble summary: inconsistent record shape";
-    return -1;
-  }
+  if (tri > a.TRI) return pass_fail(err, "ensemble summary: inconsistent record shape");
   int K = 1;
   while (K < 8 && a.d * (K * 2) <= 32) K *= 2;
   auto blocks = [&](int k) { return (long)((a.N + (long)kSumBlock * k - 1) / ((long)kSumBlock * k)); };
   while (K > 1 && blocks(K) * a.n_t < 1024) K /= 2;  // four workgroups per compute unit (256 CUs) before a lane walks further
   const int n_block = (int)blocks(K), n_wave = n_block * (kSumBlock / kWave);
   const size_t lds = (size_t)a.d * K * kSumBlock * sizeof(double);
-  if ((long)n_block * a.n_t >= (1l << 31)) {
-    err = "ensemble summary: more than 2^31 workgroups; shard the ensemble";
-    return -1;
-  }
+  if ((long)n_block * a.n_t >= (1l << 31)) return pass_fail(err, "ensemble summary: more than 2^31 workgroups; shard the ensemble");
   if (c.cap_t < a.n_t) {
-    for (void* p : {(void*)c.count, (void*)c.mean, (void*)c.within, (void*)c.between})
-      if (p) (void)hipFree(p);
-    c.count = nullptr;
-    c.mean = c.within = c.between = nullptr;
+    free_device(c.count, c.mean, c.within, c.between);
     c.cap_t = 0;
     if (hipMalloc((void**)&c.count, sizeof(long long) * a.n_t) != hipSuccess ||
         hipMalloc((void**)&c.mean, sizeof(double) * a.n_t * a.d) != hipSuccess ||
         hipMalloc((void**)&c.within, sizeof(double) * a.n_t * tri) != hipSuccess ||
         hipMalloc((void**)&c.between, sizeof(double) * a.n_t * tri) != hipSuccess) {
       (void)hipGetLastError();
-      err = "ensemble summary: out of device memory";
-      return -1;
+      return pass_fail(err, "ensemble summary: out of device memory");
     }
     c.cap_t = a.n_t;
   }
   if (!grow((void**)&st.part, &st.part_cap, sizeof(double) * (size_t)a.n_t * n_wave * R) ||
-      !grow((void**)&st.part_cnt, &st.cnt_cap, sizeof(int) * (size_t)a.n_t * n_wave)) {
-    err = "ensemble summary: out of device memory";
-    return -1;
-  }
-  for (hipEvent_t& e : st.ev)
-    if (!e && hipEventCreate(&e) != hipSuccess) {
-      err = "ensemble summary: hipEventCreate failed";
-      return -1;
-    }
-  (void)hipEventRecord(st.ev[0], stream);
+      !grow((void**)&st.part_cnt, &st.cnt_cap, sizeof(int) * (size_t)a.n_t * n_wave))
+    return pass_fail(err, "ensemble summary: out of device memory");
+  if (st.timer.begin(stream) != hipSuccess) return pass_fail(err, "ensemble summary: hipEventCreate failed");
   switch (K) {
     case 8: launch_sums<8>(a, n_block, n_wave, lds, st.part, st.part_cnt, stream); break;
     case 4: launch_sums<4>(a, n_block, n_wave, lds, st.part, st.part_cnt, stream); break;
@@ -112,14 +79,8 @@ int summary_run(SummaryState& st, SummaryCache& c, const SummaryArgs& a, hipStre
   }
   hipLaunchKernelGGL(summary_fold_kernel, dim3((unsigned)a.n_t), dim3(kWave), 0, stream, (const double*)st.part, (const int*)nullptr,
                      n_wave, tri, tri, c.count, c.between, (double*)nullptr);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipEventRecord(st.ev[1], stream);
-  if (e == hipSuccess) e = hipEventSynchronize(st.ev[1]);
-  if (e == hipSuccess && ms) e = hipEventElapsedTime(ms, st.ev[0], st.ev[1]);
-  if (e != hipSuccess) {
-    err = std::string("ensemble summary: ") + hipGetErrorString(e);
-    return -1;
-  }
+  if (const hipError_t e = st.timer.end(stream, ms); e != hipSuccess)
+    return pass_fail(err, "ensemble summary: %s", hipGetErrorString(e));
   if (n_launches) *n_launches = 4;
   c.n_t = a.n_t;
   c.valid = true;
@@ -128,15 +89,9 @@ int summary_run(SummaryState& st, SummaryCache& c, const SummaryArgs& a, hipStre
 }
 
 void summary_free(SummaryState& st) {
-  for (SummaryCache& c : st.src) {
-    for (void* p : {(void*)c.count, (void*)c.mean, (void*)c.within, (void*)c.between})
-      if (p) (void)hipFree(p);
-    c = SummaryCache{};
-  }
-  if (st.part) (void)hipFree(st.part);
-  if (st.part_cnt) (void)hipFree(st.part_cnt);
-  for (hipEvent_t& e : st.ev)
-    if (e) (void)hipEventDestroy(e);
+  for (SummaryCache& c : st.src) free_device(c.count, c.mean, c.within, c.between);
+  free_device(st.part, st.part_cnt);
+  st.timer.destroy();
   st = SummaryState{};
 }
 

@@ -99,6 +99,37 @@ DATA_FIELDS = {
 }
 K_DATA_LOGLIK = 4  # `which` of odef_kernel_time_ms / odef_kernel_name
 
+# dtype and shape (of a Context `c`) of every derived field, by family and quantity; the source does not matter
+_FLAT = lambda c: (-1,)  # noqa: E731  ([n_t] counts, [N] per-trajectory values)
+_DERIVED_LAYOUT = {
+    ("summary", S_COUNT): (np.int64, _FLAT),
+    ("summary", S_MEAN): (np.float64, lambda c: (-1, c.d)),
+    ("summary", S_COV_WITHIN): (np.float64, lambda c: (-1, c.d * (c.d + 1) // 2)),
+    ("summary", S_COV_BETWEEN): (np.float64, lambda c: (-1, c.d * (c.d + 1) // 2)),
+    ("errors", E_FINAL): (np.float64, _FLAT), ("errors", E_L2): (np.float64, _FLAT),
+    ("errors", E_LINF): (np.float64, _FLAT), ("errors", E_CHI2): (np.float64, _FLAT),
+    ("errors", E_NUSED): (np.int64, _FLAT),
+    ("errors", E_U_ANALYTIC): (np.float64, lambda c: (-1, c.d, c.N)),
+    ("data", L_DATA_LOGLIK - L_BASE): (np.float64, _FLAT), ("data", L_DATA_MAHALANOBIS - L_BASE): (np.float64, _FLAT),
+}
+_DERIVED = {S_BASE + 8 * s + q: _DERIVED_LAYOUT["summary", q] for s in range(3) for q in range(4)}
+_DERIVED.update({E_BASE + 8 * s + q: _DERIVED_LAYOUT["errors", q] for s in range(2) for q in range(6)})
+_DERIVED.update({L_BASE + q: _DERIVED_LAYOUT["data", q] for q in range(2)})
+
+
+def _fetch(lib, h, f: int, dtype=None) -> np.ndarray:
+    """Field `f` of the context handle `h` as a flat array: byte count, allocation, `odef_get`.  A refusal raises OdefError with
+    the library's message.  dtype: that of the field unless given."""
+    if dtype is None:
+        dtype = _DERIVED[f][0] if f in _DERIVED else np.int32 if f in _INT_FIELDS else np.float64
+    b = C.c_size_t()
+    if lib.odef_field_bytes(h, f, C.byref(b)) != 0:
+        raise OdefError(lib.odef_last_error(h).decode() or f"odef_field_bytes failed for field {f}")
+    out = np.empty(b.value // np.dtype(dtype).itemsize, dtype=dtype)
+    if lib.odef_get(h, f, out.ctypes.data_as(_vp), b.value) != 0:
+        raise OdefError(lib.odef_last_error(h).decode())
+    return out
+
 
 def _observation_arrays(t, d, N, times, data, noise_var, components):
     """The four inputs of the data log-likelihood in the ABI layout, validated on the host: (saves int64 [M], comps int64 [o],
@@ -341,14 +372,7 @@ class DeviceGroup:
         DIFFUSION of the MV models included)."""
         parts = []
         for g in range(self.G):
-            c = self.lib.odef_group_ctx(self._h, g)
-            b = C.c_size_t()
-            if self.lib.odef_field_bytes(c, f, C.byref(b)) != 0:
-                raise OdefError(f"odef_field_bytes failed for field {f} of shard {g}")
-            dt = np.int32 if f in _INT_FIELDS else np.float64
-            out = np.empty(b.value // np.dtype(dt).itemsize, dtype=dt)
-            if self.lib.odef_get(c, f, out.ctypes.data_as(_vp), b.value) != 0:
-                raise OdefError(self.lib.odef_last_error(c).decode())
+            out = _fetch(self.lib, self.lib.odef_group_ctx(self._h, g), f)
             n = self.shard(g)[1]
             if f in (F_MEAN, F_SMOOTH_MEAN):
                 out = out.reshape(-1, self.D, n)
@@ -371,12 +395,10 @@ class DeviceGroup:
         """Data log-likelihood of the WHOLE ensemble (`EnsembleSolution.data_loglik`): the same observations go to every shard
         through `odef_group_ctx`, per-trajectory values are split by `odef_group_shard`, every shard runs the pass on its own
         device and the results are joined along the trajectory axis.  Returns (loglik [N], mahalanobis [N])."""
-        c0 = self.lib.odef_group_ctx(self._h, 0)
-        nb = C.c_size_t()
-        self._chk_ctx(0, self.lib.odef_field_bytes(c0, F_T, C.byref(nb)))
-        t = np.empty(nb.value // 8)
-        if nb.value == 0 or self.lib.odef_get(c0, F_T, t.ctypes.data_as(_vp), nb.value) != 0:
-            raise OdefError("data_loglik: needs a fixed-grid solve first")
+        try:
+            t = _fetch(self.lib, self.lib.odef_group_ctx(self._h, 0), F_T)
+        except OdefError:
+            raise OdefError("data_loglik: needs a fixed-grid solve first") from None
         saves, comps, values, noise, per_traj = _observation_arrays(t, self.d, self.N, times, data, noise_var, components)
         self._obs_bufs = []
         parts = []
@@ -394,26 +416,14 @@ class DeviceGroup:
         parts = []
         for g in range(self.G):
             c = self.lib.odef_group_ctx(self._h, g)
-            blk = []
-            for qty in range(4):
-                f = summary_field(source, qty)
-                b = C.c_size_t()
-                self._chk_ctx(g, self.lib.odef_field_bytes(c, f, C.byref(b)))
-                out = np.empty(b.value // 8, dtype=np.int64 if qty == S_COUNT else np.float64)
-                self._chk_ctx(g, self.lib.odef_get(c, f, out.ctypes.data_as(_vp), b.value))
-                blk.append(out if qty == S_COUNT else out.reshape(len(blk[0]), -1))
-            parts.append(tuple(blk))
+            parts.append(tuple(_fetch(self.lib, c, f).reshape(_DERIVED[f][1](self))
+                               for f in (summary_field(source, qty) for qty in range(4))))
         return merge_moments(parts)
 
     def summary(self, smoothed: bool = False) -> "EnsembleSummary":
         """`EnsembleSummary` of the whole ensemble on the save grid of a fixed-grid solve."""
         n, m, w, b = self.ensemble_moments(S_SOURCE_SMOOTH if smoothed else S_SOURCE_FILTER)
-        c = self.lib.odef_group_ctx(self._h, 0)
-        nb = C.c_size_t()
-        self._chk_ctx(0, self.lib.odef_field_bytes(c, F_T, C.byref(nb)))
-        t = np.empty(nb.value // 8)
-        self._chk_ctx(0, self.lib.odef_get(c, F_T, t.ctypes.data_as(_vp), nb.value))
-        return EnsembleSummary.from_moments(t, n, m, w, b)
+        return EnsembleSummary.from_moments(_fetch(self.lib, self.lib.odef_group_ctx(self._h, 0), F_T), n, m, w, b)
 
     def shard_kernel_ms(self, which=0):
         ms = []
@@ -542,31 +552,20 @@ class Context:
         """Posterior at the times `tq` for every trajectory: (mean [n_q, D, N], cov_tril [n_q, TRI, N])."""
         tq = np.ascontiguousarray(tq, dtype=np.float64)
         self._chk(self.lib.odef_dense_output(self._h, _as_dp(tq), len(tq), int(smoothed)))
-        nb = self.field_bytes(F_DENSE_MEAN)
-        m = np.empty(nb // 8)
-        self._chk(self.lib.odef_get(self._h, F_DENSE_MEAN, m.ctypes.data_as(_vp), nb))
-        nb = self.field_bytes(F_DENSE_COV_TRIL)
-        c = np.empty(nb // 8)
-        self._chk(self.lib.odef_get(self._h, F_DENSE_COV_TRIL, c.ctypes.data_as(_vp), nb))
+        m, c = _fetch(self.lib, self._h, F_DENSE_MEAN), _fetch(self.lib, self._h, F_DENSE_COV_TRIL)
         return m.reshape(len(tq), self.D, self.N), c.reshape(len(tq), self.TRI, self.N)
 
     def sample_states(self, n: int, seed: int, noise_scale: float = 1.0):
         """n joint posterior draws of the state path per trajectory: [n_save, D, n, N]."""
         self._chk(self.lib.odef_sample(self._h, int(n), int(seed) & 0xFFFFFFFFFFFFFFFF, float(noise_scale)))
-        nb = self.field_bytes(F_SAMPLES)
-        a = np.empty(nb // 8)
-        self._chk(self.lib.odef_get(self._h, F_SAMPLES, a.ctypes.data_as(_vp), nb))
-        return a.reshape(self.n_save, self.D, int(n), self.N)
+        return _fetch(self.lib, self._h, F_SAMPLES).reshape(self.n_save, self.D, int(n), self.N)
 
     def dense_sample_states(self, tq, n: int, seed: int, noise_scale: float = 1.0):
         """n joint draws of the state path on the times tq (filter-interpolated states): [n_q, D, n, N]."""
         tq = np.ascontiguousarray(tq, float)
         self._chk(self.lib.odef_dense_sample(self._h, tq.ctypes.data_as(C.POINTER(C.c_double)), len(tq), int(n),
                                              int(seed) & 0xFFFFFFFFFFFFFFFF, float(noise_scale)))
-        nb = self.field_bytes(F_SAMPLES)
-        a = np.empty(nb // 8)
-        self._chk(self.lib.odef_get(self._h, F_SAMPLES, a.ctypes.data_as(_vp), nb))
-        return a.reshape(len(tq), self.D, int(n), self.N)
+        return _fetch(self.lib, self._h, F_SAMPLES).reshape(len(tq), self.D, int(n), self.N)
 
     def synchronize(self):
         self._chk(self.lib.odef_synchronize(self._h))
@@ -582,20 +581,10 @@ class Context:
 
     def get(self, f: int) -> np.ndarray:
         """Field in the device layout (include/odefilter.h), as a flat numpy array reshaped."""
-        nbytes = self.field_bytes(f)
-        dt = np.int32 if f in _INT_FIELDS else np.float64
-        if _is_summary_field(f):  # [n_t] int64 counts, [n_t, d] means, [n_t, d(d+1)/2] packed covariances
-            dt = np.int64 if (f - S_BASE) % 8 == S_COUNT else np.float64
-        if _is_errors_field(f):  # [N] per trajectory (NUSED int64), U_ANALYTIC [n_save, d, N]
-            dt = np.int64 if (f - E_BASE) % 8 == E_NUSED else np.float64
-        out = np.empty(nbytes // np.dtype(dt).itemsize, dtype=dt)
-        self._chk(self.lib.odef_get(self._h, f, out.ctypes.data_as(_vp), nbytes))
-        if _is_summary_field(f):
-            qty = (f - S_BASE) % 8
-            return out if qty == S_COUNT else out.reshape(-1, self.d if qty == S_MEAN else self.d * (self.d + 1) // 2)
+        out = _fetch(self.lib, self._h, f)
+        if f in _DERIVED:
+            return out.reshape(_DERIVED[f][1](self))
         ns, N = self.n_save, self.N
-        if _is_errors_field(f):
-            return out.reshape(ns, self.d, N) if (f - E_BASE) % 8 == E_U_ANALYTIC else out
         if f in (F_MEAN, F_SMOOTH_MEAN):
             return out.reshape(ns, self.D, N)
         if f in (F_COV_TRIL, F_SMOOTH_COV_TRIL):
@@ -618,16 +607,8 @@ class Context:
 
     @staticmethod
     def _solution_errors(lib, h, source: int):
-        out = {}
-        for key, qty in (("l∞", E_LINF), ("l2", E_L2), ("final", E_FINAL), ("chi2", E_CHI2), ("nused", E_NUSED)):
-            f, b = errors_field(source, qty), C.c_size_t()
-            if lib.odef_field_bytes(h, f, C.byref(b)) != 0:
-                raise OdefError(lib.odef_last_error(h).decode())
-            a = np.empty(b.value // 8, dtype=np.int64 if qty == E_NUSED else np.float64)
-            if lib.odef_get(h, f, a.ctypes.data_as(_vp), b.value) != 0:
-                raise OdefError(lib.odef_last_error(h).decode())
-            out[key] = a
-        return out
+        return {key: _fetch(lib, h, errors_field(source, qty))
+                for key, qty in (("l∞", E_LINF), ("l2", E_L2), ("final", E_FINAL), ("chi2", E_CHI2), ("nused", E_NUSED))}
 
     def solution_errors(self, source: int):
         """Per-trajectory errors of the filter (0) or smoothed (1) solution against the truth -- the vector field's `analytic`, or
@@ -655,16 +636,7 @@ class Context:
             for f, b in zip((L_OBS_SAVE, L_OBS_COMPONENT, L_OBS_VALUE, L_OBS_NOISE), bufs):
                 if lib.odef_bind_device(h, f, _vp(b.data_ptr()), b.numel() * 8) != 0:
                     raise OdefError(lib.odef_last_error(h).decode())
-        out = []
-        for f in (L_DATA_LOGLIK, L_DATA_MAHALANOBIS):
-            b = C.c_size_t()
-            if lib.odef_field_bytes(h, f, C.byref(b)) != 0:
-                raise OdefError(lib.odef_last_error(h).decode())
-            a = np.empty(b.value // 8)
-            if lib.odef_get(h, f, a.ctypes.data_as(_vp), b.value) != 0:
-                raise OdefError(lib.odef_last_error(h).decode())
-            out.append(a)
-        return tuple(out)
+        return tuple(_fetch(lib, h, f) for f in (L_DATA_LOGLIK, L_DATA_MAHALANOBIS))
 
     def data_loglik(self):
         """Per-trajectory log-likelihood of the bound observations under the posterior of the last fixed-grid solve, and the

@@ -113,6 +113,36 @@ def test_requests_repeat_bit_for_bit_and_follow_a_new_solve(pkg):
         assert not np.array_equal(_got(ctx, 0)["l2"], got["l2"])
 
 
+def test_records_edited_through_their_device_pointer_reach_the_next_errors(pkg):
+    """odef_get_device hands out a writable pointer, so it drops what is derived from that record set (include/odefilter.h,
+    "Derived outputs and their caches"): after F_MEAN is doubled in place the next request runs the pass again, on the records as
+    they are now.  (n_launches of this pass is set per pass, not counted up: that the pass ran anew shows in the values.)"""
+    import torch
+
+    h = _host()
+    vf = orc.vector_field("linear")
+    N = 70
+    u0s = _u0s(N, 2, vf.u0, 7)
+    with pkg.Context("linear", 2, h.EK0_ID, N) as ctx:
+        ctx.set_problem(u0s, vf.p, 0.0)
+        ctx.solve_fixed(np.arange(9) * 2.0 ** -6)
+        truth = er.linear_truth(u0s, vf.p, ctx.get(h.F_T))
+        first, _ = _check(ctx, 0, truth, False, "before the edit")
+        ptr, nbytes = ctx.device_ptr(h.F_MEAN)
+
+        class Raw:
+            __cuda_array_interface__ = {"shape": (nbytes // 8,), "typestr": "<f8", "data": (ptr, False), "version": 2}
+
+        torch.as_tensor(Raw(), device="cuda").mul_(2.0)
+        torch.cuda.synchronize()
+        second, _ = _check(ctx, 0, truth, False, "F_MEAN doubled")  # the reference reads the records back: the doubled ones
+        ms, nl = ctx.kernel_time_ms(3)
+        assert ms > 0 and nl == 2
+        for k in er.KEYS:
+            assert not np.array_equal(second[k], first[k]), k
+        assert np.array_equal(second["nused"], first["nused"])
+
+
 DECAY = """
 struct NAME {
   static constexpr int d = 1, np = 1;

@@ -547,6 +547,46 @@ def test_pleiades_smoother_record_stage(pkg, q, monkeypatch):
     assert (np.abs(out["split"][1] - out["whole"][1]) <= (1e-12 if q < 5 else 1e-8) * scale + 1e-300).all()
 
 
+def test_pleiades_smoother_reads_records_edited_after_the_solve(pkg, monkeypatch):
+    """The filter leaves its covariance records in the trajectory-major stage and the smoother that follows reads them there
+    (the resident path of test_pleiades_smoother_record_stage, "whole").  odef_get_device of a filter record hands out a writable
+    pointer and ends that residency (include/odefilter.h, "Derived outputs and their caches"): COV_TRIL scaled by 4 between
+    solve and smooth must reach the smoother with the default stage as it does with the records in place (budget 0).  The two
+    paths are bit-identical on equal records (the test above)."""
+    import torch
+
+    vf = orc.vector_field("pleiades")
+    N, dt = 70, 2.0**-10
+    grid = np.concatenate([np.arange(8) * dt, 7 * dt + np.arange(1, 7) * dt / 2])  # 14 records
+    monkeypatch.setenv("ODEF_SMOOTH_SPLIT", "0")
+    out = {}
+    for name, mb, edit in (("resident", None, True), ("in place", "0", True), ("unedited", None, False)):
+        if mb is None:
+            monkeypatch.delenv("ODEF_SMOOTH_STAGE_MB", raising=False)
+        else:
+            monkeypatch.setenv("ODEF_SMOOTH_STAGE_MB", mb)
+        ctx = pkg.Context("pleiades", 2, 1, N, save_everystep=True)
+        ctx.set_problem_perturbed(vf.u0, [], 0.0, 1e-3, n_perturbed=14)
+        ctx.solve_fixed(grid)
+        if edit:
+            ptr, nbytes = ctx.device_ptr(1)
+
+            class Raw:
+                __cuda_array_interface__ = {"shape": (nbytes // 8,), "typestr": "<f8", "data": (ptr, False), "version": 2}
+
+            torch.as_tensor(Raw(), device="cuda").mul_(4.0)
+            torch.cuda.synchronize()
+        ctx.smooth()
+        assert (ctx.get(10) == 0).all(), name
+        out[name] = (ctx.get(11).copy(), ctx.get(12).copy())
+        ctx.close()
+    assert np.isfinite(out["resident"][0]).all() and np.isfinite(out["resident"][1]).all()
+    np.testing.assert_array_equal(out["resident"][0], out["in place"][0])
+    np.testing.assert_array_equal(out["resident"][1], out["in place"][1])
+    assert not np.array_equal(out["resident"][0], out["unedited"][0])
+    assert not np.array_equal(out["resident"][1], out["unedited"][1])
+
+
 @pytest.mark.parametrize("kind,q", [("EK1", 2), ("EK0", 3), ("EK1", 5)])
 def test_pleiades_adaptive(pkg, kind, q):
     """The reference's default solve is adaptive: PI-controlled steps on the workgroup-per-trajectory path

@@ -160,6 +160,34 @@ def test_two_requests_agree_bit_for_bit_and_the_device_copy_equals_the_host_copy
             ctx.bind_device(h.summary_field(0, 1), 0, 0)
 
 
+def test_records_edited_through_their_device_pointer_reach_the_next_summary(pkg):
+    """odef_get_device hands out a writable pointer, so it drops what is derived from that record set (include/odefilter.h,
+    "Derived outputs and their caches").  N = 70: one full and one partial wavefront.  Scaling by a power of two is exact and the
+    summation order is fixed, so MEAN doubles and COV_BETWEEN quadruples bit for bit; COV_WITHIN reads the covariances only."""
+    import torch
+
+    h = _host()
+    vf = orc.vector_field("lorenz63")
+    N = 70
+    with pkg.Context("lorenz63", 2, h.EK1_ID, N) as ctx:
+        ctx.set_problem_perturbed(vf.u0, vf.p, 0.0, 1e-3)
+        ctx.solve_fixed(np.arange(9) * 2.0**-6)
+        n0, m0, w0, b0 = ctx.ensemble_moments(0)
+        assert np.all(n0 == N) and np.all(np.isfinite(m0)) and np.any(m0 != 0)
+        ptr, nbytes = ctx.device_ptr(h.F_MEAN)
+
+        class Raw:
+            __cuda_array_interface__ = {"shape": (nbytes // 8,), "typestr": "<f8", "data": (ptr, False), "version": 2}
+
+        torch.as_tensor(Raw(), device="cuda").mul_(2.0)
+        torch.cuda.synchronize()
+        n1, m1, w1, b1 = ctx.ensemble_moments(0)
+        assert n1.tobytes() == n0.tobytes()
+        assert m1.tobytes() == (2.0 * m0).tobytes()
+        assert b1.tobytes() == (4.0 * b0).tobytes()
+        assert w1.tobytes() == w0.tobytes()
+
+
 def test_two_shards_merge_to_the_one_context_summary(pkg):
     h = _host()
     vf = orc.vector_field("lorenz63")
