@@ -13,6 +13,7 @@
 #include "dense_rows.h"
 #include "sample_rows.h"
 #include "launch.h"
+#include "wave_map.h"
 
 namespace odef {
 
@@ -30,7 +31,7 @@ __device__ __attribute__((always_inline)) inline void stagger_start(const Filter
 }
 template <class RHS, int q, bool EK1, bool EVERY, bool LAG = false>
 __global__ __launch_bounds__(kWave) void ek_filter_fixed_kernel(const FilterParams P) {
-  const long i0 = (long)blockIdx.x * kWave;  // wave-uniform
+  const long i0 = wave_first_trajectory(blockIdx.x, gridDim.x, P.wave_map);  // wave-uniform, once, in front of the time loop
   stagger_start(P);
   if (i0 + threadIdx.x < P.N) filter_fixed_lane<RHS, q, EK1, EVERY, LAG>(P, i0, threadIdx.x);
 }
@@ -43,7 +44,7 @@ __global__ __launch_bounds__(kWave) void ek_filter_adaptive_kernel(const FilterP
 // record.  Kernels of their own, so that the scalar-model kernels above stay what they are.
 template <class RHS, int q, bool EVERY, bool LAG>
 __global__ __launch_bounds__(kWave) void ek_filter_fixed_mv_kernel(const FilterParams P) {
-  const long i0 = (long)blockIdx.x * kWave;
+  const long i0 = wave_first_trajectory(blockIdx.x, gridDim.x, P.wave_map);
   stagger_start(P);
   if (i0 + threadIdx.x < P.N) filter_fixed_lane<RHS, q, false, EVERY, LAG, true>(P, i0, threadIdx.x);
 }
@@ -56,7 +57,7 @@ __global__ __launch_bounds__(kWave) void ek_filter_adaptive_mv_kernel(const Filt
 // kernel of its own, so that the EK1 kernels above stay what they are.
 template <class RHS, int q, bool LAG>
 __global__ __launch_bounds__(kWave) void ek_filter_fixed_ieks_kernel(const FilterParams P) {
-  const long i0 = (long)blockIdx.x * kWave;
+  const long i0 = wave_first_trajectory(blockIdx.x, gridDim.x, P.wave_map);
   stagger_start(P);
   if (i0 + threadIdx.x < P.N) filter_fixed_lane<RHS, q, true, true, LAG, false, true>(P, i0, threadIdx.x);
 }
@@ -97,9 +98,21 @@ constexpr int kSmoothLaneMaxD = 12;
 constexpr long kSmoothLaneMinN = 6144;
 inline long smooth_lane_min_n() { return env_long("ODEF_SMOOTH_LANE_MIN_N", kSmoothLaneMinN); }
 // Ensemble size below which the every-step filter stores its records lagged by one step (LaggedSink, ek_lane.h);
-// ODEF_FILTER_LAG_MAX_N overrides it (read at every launch).
-constexpr long kFilterLagMaxN = 32768;
+// ODEF_FILTER_LAG_MAX_N overrides it (read at every launch).  On today's kernel the lagged form is the slower one wherever it
+// was measured (Lorenz-63 EK1(3), 1 024 steps, lane filter forced: 4.88 / 4.91 / 5.10 ms against 4.54 / 4.56 / 4.67 ms at
+// 4 096 / 16 384 / 24 576 trajectories, profiles/r04_lag_ab.jsonl), so it ends where the scalar models leave the row-team
+// filter for the lane filter (kFilterRowsMaxN): no ensemble that reaches the lane filter by default stores lagged.  Below that
+// size it stays what a forced lane filter and the models without a row-team filter (MV, D > 16; not measured) get.
+constexpr long kFilterLagMaxN = kFilterRowsMaxN;
 inline long filter_lag_max_n() { return env_long("ODEF_FILTER_LAG_MAX_N", kFilterLagMaxN); }
+// Wave -> trajectory map of the fixed-step lane filter kernels (wave_map.h): 0 = identity, 1 = XCD-contiguous.
+// ODEF_WAVE_MAP overrides it (read at every launch, so that both maps can be timed alternately within one process).
+// Measured that way on the headline workload (65 536 x 1 024, every step saved; profiles/r04_wave_map_ab.jsonl): 8.85 ms under
+// map 1 against 9.25 / 9.27 ms under map 0, -4.3 % with the two map-0 series 0.2 % apart; ensembles of 4 096 - 24 576
+// trajectories (fewer waves than SIMDs) run the same under either map, within 0.1 %.
+static_assert(kWaveMapLanes == kWave, "wave_map.h counts trajectories in wavefronts of the lane kernels");
+constexpr long kWaveMapDefault = 1;
+inline int wave_map_mode() { return (int)env_long("ODEF_WAVE_MAP", kWaveMapDefault); }
 // Two kernels (fixed grid / adaptive records) so that each gets its own register allocation.
 template <int d, int q, bool ADAPT>
 __global__ __launch_bounds__(kWave) void rts_smooth_lane_kernel(const SmoothParams P) {
@@ -360,20 +373,22 @@ struct LaunchFilterT {
       }
     }
     const bool lag = P.everystep && P.N < filter_lag_max_n();  // small ensemble: spread the record stores over the next step
+    FilterParams Pw = P;  // this launch's copy: the wave map is chosen here
+    Pw.wave_map = wave_map_mode();
     if constexpr (M == kIeks) {
       note_kernel("odef::ek_filter_fixed_ieks_kernel<odef::%s, %d, %s>", RHS::name, q, tf(lag));
-      if (lag) hipLaunchKernelGGL((ek_filter_fixed_ieks_kernel<RHS, q, true>), grid, dim3(kWave), 0, s, P);
-      else hipLaunchKernelGGL((ek_filter_fixed_ieks_kernel<RHS, q, false>), grid, dim3(kWave), 0, s, P);
+      if (lag) hipLaunchKernelGGL((ek_filter_fixed_ieks_kernel<RHS, q, true>), grid, dim3(kWave), 0, s, Pw);
+      else hipLaunchKernelGGL((ek_filter_fixed_ieks_kernel<RHS, q, false>), grid, dim3(kWave), 0, s, Pw);
     } else if constexpr (M == kMv) {
       note_kernel("odef::ek_filter_fixed_mv_kernel<odef::%s, %d, %s, %s>", RHS::name, q, tf(P.everystep), tf(lag));
-      if (lag) hipLaunchKernelGGL((ek_filter_fixed_mv_kernel<RHS, q, true, true>), grid, dim3(kWave), 0, s, P);
-      else if (P.everystep) hipLaunchKernelGGL((ek_filter_fixed_mv_kernel<RHS, q, true, false>), grid, dim3(kWave), 0, s, P);
-      else hipLaunchKernelGGL((ek_filter_fixed_mv_kernel<RHS, q, false, false>), grid, dim3(kWave), 0, s, P);
+      if (lag) hipLaunchKernelGGL((ek_filter_fixed_mv_kernel<RHS, q, true, true>), grid, dim3(kWave), 0, s, Pw);
+      else if (P.everystep) hipLaunchKernelGGL((ek_filter_fixed_mv_kernel<RHS, q, true, false>), grid, dim3(kWave), 0, s, Pw);
+      else hipLaunchKernelGGL((ek_filter_fixed_mv_kernel<RHS, q, false, false>), grid, dim3(kWave), 0, s, Pw);
     } else {
       note_kernel("odef::ek_filter_fixed_kernel<odef::%s, %d, %s, %s, %s>", RHS::name, q, tf(EK1), tf(P.everystep), tf(lag));
-      if (lag) hipLaunchKernelGGL((ek_filter_fixed_kernel<RHS, q, EK1, true, true>), grid, dim3(kWave), 0, s, P);
-      else if (P.everystep) hipLaunchKernelGGL((ek_filter_fixed_kernel<RHS, q, EK1, true>), grid, dim3(kWave), 0, s, P);
-      else hipLaunchKernelGGL((ek_filter_fixed_kernel<RHS, q, EK1, false>), grid, dim3(kWave), 0, s, P);
+      if (lag) hipLaunchKernelGGL((ek_filter_fixed_kernel<RHS, q, EK1, true, true>), grid, dim3(kWave), 0, s, Pw);
+      else if (P.everystep) hipLaunchKernelGGL((ek_filter_fixed_kernel<RHS, q, EK1, true>), grid, dim3(kWave), 0, s, Pw);
+      else hipLaunchKernelGGL((ek_filter_fixed_kernel<RHS, q, EK1, false>), grid, dim3(kWave), 0, s, Pw);
     }
   }
 };

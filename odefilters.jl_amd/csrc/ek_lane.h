@@ -31,6 +31,7 @@ struct FilterParams {
   // options
   int everystep, fixed_diffusion, want_loglik;
   int stagger;  // start skew between wavefronts in units of s_sleep (64 clocks); 0 = off
+  int wave_map;  // which trajectories a wavefront of the fixed-step lane filter owns (wave_map.h); 0 = identity
   // outputs
   double* mean;    // [n_save][D][N]
   double* cov;     // [n_save][TRI][N]
