@@ -283,14 +283,14 @@ class DeviceGroup:
     julia/ODEFilterHIP.jl) -- contiguous blocks, no exchange while stepping, `allgather()` = the one RCCL collective."""
 
     def __init__(self, rhs: str, order: int, alg: int, n_traj: int, n_devices: int, *, device_ids=None, diffusion="dynamic",
-                 smooth=False, save_everystep=True, want_loglik=True):
+                 smooth=False, save_everystep=True, want_loglik=True, params_shared=True):
         self.lib = load_library()
         d, npar = RHS_DIMS[rhs]
         cfg = OdefConfig()
         cfg.struct_size = C.sizeof(OdefConfig)
         cfg.alg, cfg.order, cfg.diffusion = alg, order, DIFFUSION[diffusion]
         cfg.smooth, cfg.rhs_id, cfg.d, cfg.n_params = int(smooth), RHS[rhs], d, npar
-        cfg.params_shared = 1
+        cfg.params_shared = int(params_shared)  # False: `set_problem` takes p [N, n_params], every shard its rows
         cfg.save_mode = SAVE_EVERYSTEP if (save_everystep or smooth) else SAVE_FINAL
         cfg.device, cfg.want_loglik, cfg.n_traj = -1, int(want_loglik), n_traj
         self.d, self.D, self.N, self.G = d, d * (order + 1), n_traj, n_devices

@@ -87,9 +87,9 @@ def unpack_tril(c, D):
 
 def emul_solve(rhs_id, d, q, ek1, u0s, p, *, team=False, tgrid=None, adaptive=False, t0=0.0, t1=1.0, abstol=1e-6, reltol=1e-3,
                dt0=1e-2, max_save=4096, everystep=True, fixed_diffusion=False, want_loglik=True, smooth=False,
-               ctrl=None, dense_t=None, sample=None, dense_sample=None):
-    """u0s [N, d]; p [np] shared.  Returns dict of numpy arrays in the device layout transposed
-    to trajectory-major: mean [N, n_save, D], cov [N, n_save, D, D] ..."""
+               ctrl=None, dense_t=None, sample=None, dense_sample=None, ps=None):
+    """u0s [N, d]; p [np] shared, or ps [N, np] per trajectory (handed over as the device keeps it, [np][N]).
+    Returns dict of numpy arrays in the device layout transposed to trajectory-major: mean [N, n_save, D], cov [N, n_save, D, D] ..."""
     u0s = np.asarray(u0s, float)
     N = u0s.shape[0]
     D = d * (q + 1)
@@ -97,11 +97,15 @@ def emul_solve(rhs_id, d, q, ek1, u0s, p, *, team=False, tgrid=None, adaptive=Fa
     At, Qt, QLt = prior_tables(q)
     u0_dev = np.ascontiguousarray(u0s.T)
     p = np.ascontiguousarray(np.asarray(p, float)) if len(p) else np.zeros(1)
+    if ps is not None:
+        ps = np.asarray(ps, float)
+        assert ps.shape == (N, len(p)), ps.shape
+        p = np.ascontiguousarray(ps.T)
     if ctrl is None:
         ctrl = np.array([7.0 / (10 * (q + 1)), 2.0 / (5 * (q + 1)), 0.9, 0.2, 10.0, 1.0, 1.0, 1e-4, 0.0, 1e300])
     a = EmulArgs()
     a.rhs, a.q, a.ek1, a.adaptive = rhs_id, q, int(ek1), int(adaptive)
-    a.N, a.u0, a.p, a.p_shared = N, _p(u0_dev), _p(p), 1
+    a.N, a.u0, a.p, a.p_shared = N, _p(u0_dev), _p(p), int(ps is None)
     a.At, a.Qt, a.QLt = _p(At), _p(Qt), _p(QLt)
     if adaptive:
         n_save = max_save

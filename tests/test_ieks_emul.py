@@ -31,14 +31,15 @@ def lib():
     return _LIB
 
 
-def emul_ieks(rhs_id, d, q, u0s, p, grid, model, iterations, kernel):
-    """solve_ieks on the emulated kernels: [per iteration] (smoothed mean [N, n_t, D], filter mean, loglik, njac)."""
+def emul_ieks(rhs_id, d, q, u0s, p, grid, model, iterations, kernel, ps=None):
+    """solve_ieks on the emulated kernels: [per iteration] (smoothed mean [N, n_t, D], filter mean, loglik, njac).
+    ps: parameters per trajectory [N, n_params] in place of the shared p."""
     u0s = np.asarray(u0s, float)
     N, D = u0s.shape[0], d * (q + 1)
     TRI = D * (D + 1) // 2
     At, Qt, QLt = em.prior_tables(q)
     u0_dev = np.ascontiguousarray(u0s.T)
-    p = np.ascontiguousarray(np.asarray(p, float))
+    p = np.ascontiguousarray(np.asarray(p, float) if ps is None else np.asarray(ps, float).T)
     tg = np.ascontiguousarray(np.asarray(grid, float))
     hs = np.ascontiguousarray(np.diff(tg))
     nsteps, n_save = len(hs), len(tg)
@@ -50,7 +51,7 @@ def emul_ieks(rhs_id, d, q, u0s, p, grid, model, iterations, kernel):
     ctrl = np.zeros(10)
     a = em.EmulArgs()
     a.rhs, a.q, a.ek1, a.adaptive = rhs_id, q, 1, 0
-    a.N, a.u0, a.p, a.p_shared = N, em._p(u0_dev), em._p(p), 1
+    a.N, a.u0, a.p, a.p_shared = N, em._p(u0_dev), em._p(p), int(ps is None)
     a.At, a.Qt, a.QLt = em._p(At), em._p(Qt), em._p(QLt)
     a.hs, a.ptab, a.tab_idx, a.nsteps = em._p(hs), em._p(ptab), em._p(tab_idx, em.ip), nsteps
     a.t0, a.ctrl, a.max_save = float(tg[0]), em._p(ctrl), 0

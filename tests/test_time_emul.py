@@ -37,9 +37,10 @@ def lib():
     return _LIB
 
 
-def emul_time(q, ek1, u0s, p, model, kernel, *, grid=None, adaptive=None, lin=None, everystep=True, smooth=True):
+def emul_time(q, ek1, u0s, p, model, kernel, *, grid=None, adaptive=None, lin=None, everystep=True, smooth=True, ps=None):
     """One solve of `forced` on the emulated kernels.  grid: fixed grid; adaptive: dict(t0, t1, abstol, reltol, dt0, max_save).
-    Returns the device layout transposed to trajectory-major, as _emul.emul_solve does."""
+    ps: parameters per trajectory [N, 3] in place of the shared p.  Returns the device layout transposed to trajectory-major,
+    as _emul.emul_solve does."""
     d = 2
     u0s = np.asarray(u0s, float)
     N, D = u0s.shape[0], d * (q + 1)
@@ -47,11 +48,11 @@ def emul_time(q, ek1, u0s, p, model, kernel, *, grid=None, adaptive=None, lin=No
     mv = MODELS[model] >= 3
     At, Qt, QLt = em.prior_tables(q)
     u0_dev = np.ascontiguousarray(u0s.T)
-    p = np.ascontiguousarray(np.asarray(p, float))
+    p = np.ascontiguousarray(np.asarray(p, float) if ps is None else np.asarray(ps, float).T)
     ctrl = np.array([7.0 / (10 * (q + 1)), 2.0 / (5 * (q + 1)), 0.9, 0.2, 10.0, 1.0, 1.0, 1e-4, 0.0, 1e300])
     a = em.EmulArgs()
     a.rhs, a.q, a.ek1, a.adaptive = tr.RHS_FORCED, q, int(ek1), int(adaptive is not None)
-    a.N, a.u0, a.p, a.p_shared = N, em._p(u0_dev), em._p(p), 1
+    a.N, a.u0, a.p, a.p_shared = N, em._p(u0_dev), em._p(p), int(ps is None)
     a.At, a.Qt, a.QLt = em._p(At), em._p(Qt), em._p(QLt)
     if adaptive is None:
         tg = np.ascontiguousarray(np.asarray(grid, float))
