@@ -87,9 +87,12 @@ def unpack_tril(c, D):
 
 def emul_solve(rhs_id, d, q, ek1, u0s, p, *, team=False, tgrid=None, adaptive=False, t0=0.0, t1=1.0, abstol=1e-6, reltol=1e-3,
                dt0=1e-2, max_save=4096, everystep=True, fixed_diffusion=False, want_loglik=True, smooth=False,
-               ctrl=None, dense_t=None, sample=None, dense_sample=None, ps=None):
+               ctrl=None, dense_t=None, sample=None, dense_sample=None, ps=None, rescale_static=False):
     """u0s [N, d]; p [np] shared, or ps [N, np] per trajectory (handed over as the device keeps it, [np][N]).
-    Returns dict of numpy arrays in the device layout transposed to trajectory-major: mean [N, n_save, D], cov [N, n_save, D, D] ..."""
+    Returns dict of numpy arrays in the device layout transposed to trajectory-major: mean [N, n_save, D], cov [N, n_save, D, D] ...
+    rescale_static: with a static diffusion model the step code leaves unscaled covariances and the running global diffusion;
+    the library's postamble kernel (api.hip scale_cov_kernel: Sigma *= final, diffusions .= final, log-likelihood NaN) runs between
+    filter and smoother -- restated here record by record, one multiplication each, so that the smoother sees what it sees there."""
     u0s = np.asarray(u0s, float)
     N = u0s.shape[0]
     D = d * (q + 1)
@@ -139,6 +142,12 @@ def emul_solve(rhs_id, d, q, ek1, u0s, p, *, team=False, tgrid=None, adaptive=Fa
     fn = lib().emul_filter_tiles if team == "tiles" else (lib().emul_filter_team if team else lib().emul_filter)
     rc = fn(C.byref(a))
     assert rc == 0, rc
+    if rescale_static:
+        assert fixed_diffusion and not adaptive and int(everystep) > 0
+        final = diff[n_save - 1].copy()
+        cov *= final[None, None, :]
+        diff[1:] = final[None, :]
+        loglik[:] = np.nan
     out = dict(mean=mean.transpose(2, 0, 1), cov=unpack_tril(cov.transpose(2, 0, 1), D), diff=diff.T, tsave=tsave.T,
                loglik=loglik, naccept=ints[0], nreject=ints[1], nf=ints[2], njac=ints[3], nsaved=ints[4],
                retcode=ints[5], tgrid=tg)

@@ -18,13 +18,27 @@ exact result there).  So "the device agrees with the oracle to x" is the wrong q
                          the D = 168 kernels' parity tests are measured against (round 3; until then their tolerance was
                          calibrated on the float64 oracle's own spread, and the order-5 covariances were not compared at all)
 
+  exact_small_<field>_<ek0|ek1>q<order>[_fixed]_ld.npz  (python tests/golden/make_exact.py --small)
+                         every other instantiation of the lane and row-team filters and of the three small-state smoothers
+                         (D = 4 ... 18, orders 1 ... 5, EK0, the `fixed` diffusion model, d = 2, a non-dyadic step): 64 steps,
+                         trajectories 0-3 of ensemble_u0(u0, 4, 1e-2), filter AND smoother, covariances of every record,
+                         diffusions and log-likelihood, longdouble (SMALL_CASES below)
+  exact_lorenz96_{ek1q2,ek1q3,ek0q3,ek1q5}_smooth_ld.npz  (--small as well)
+                         Lorenz-96 (d = 16) on the matrix-core kernels, 12 steps of dt = 2^-7, trajectories 0 and 5, the layout
+                         of the Pleiades fixtures
+
 and, next to them, the float64 oracle's distance from them per derivative block and for the covariance.  Any
 mathematically equivalent formulation gives the same exact result, so the recursion is written in the plain covariance
 form (Sigma^- = A Sigma A' + sigma^2 Q, K = Sigma^- H' S^-1, Sigma = (I - K H) Sigma^- (I - K H)'; G = Sigma A' (Sigma^-)^-1)
 in preconditioned coordinates.  (The Joseph form of the update matters even at 50 digits: Sigma^- - K S K' amplifies
 rounding errors by ~6x per step on this problem and is useless after 60 steps.)
 
-Run (build container, ~3 min):  python tests/golden/make_exact.py
+A fixture is only as sharp as the oracle's diffusion estimates are: where the residuals are rounding noise in float64 (Pleiades
+order 5 at dt = 2^-10: 0.4 relative and worse) "the oracle's distance" is a lottery ticket.  The --small entry asserts the
+admission condition max |sigma^2_oracle - sigma^2_exact| / sigma^2_exact <= 1e-4 for every fixture trajectory before it writes.
+
+Run (build container, ~3 min):  python tests/golden/make_exact.py            the Lorenz-63 / Pleiades fixtures
+                  (~1 min):     python tests/golden/make_exact.py --small    the small-state and Lorenz-96 fixtures
 """
 import math
 import os
@@ -37,6 +51,7 @@ sys.path.insert(0, os.path.join(HERE, "..", "..", "oracle"))
 sys.path.insert(0, os.path.join(HERE, ".."))
 import odefilter_oracle as orc  # noqa: E402
 from _parity import block_err, cov_err  # noqa: E402
+from _exact_cases import LORENZ96_CASES, SMALL_CASES, SMALL_NSTEPS, SMALL_NTRAJ, lorenz96_name, small_name  # noqa: E402
 
 
 # ---------------------------------------------------------------------------------------------- mpmath, Lorenz-63
@@ -152,7 +167,7 @@ def solve_spd_ld(S, B):
 
 class JetLD:
     """Truncated Taylor arithmetic on longdouble coefficients (the oracle's Jet is float64 by construction): just what the
-    Pleiades field needs -- +, -, *, real powers."""
+    oracle's vector fields need -- +, -, *, division by a scalar, real powers."""
 
     def __init__(self, c):
         self.c = np.asarray(c, dtype=np.longdouble)
@@ -183,6 +198,13 @@ class JetLD:
         return JetLD([np.dot(self.c[: k + 1], o.c[k::-1]) for k in range(n)])
 
     __rmul__ = __mul__
+
+    def __neg__(self):
+        return JetLD(-self.c)
+
+    def __truediv__(self, o):  # by a scalar only (u^3 / 3.0 of the FitzHugh-Nagumo field)
+        assert not isinstance(o, JetLD)
+        return JetLD(self.c / np.longdouble(o))
 
     def __pow__(self, a):
         n = len(self.c)
@@ -218,17 +240,50 @@ def pleiades_jac_ld(u):
     return J
 
 
-def filter_ld(vf, u0, q, dt, nsteps, kind="EK1", with_smoother=False):
-    """Pleiades only (its f is written for any scalar type, its Jacobian is restated above in longdouble).  EK0 / EK1 filter and,
-    if asked, the RTS pass (src/smoothing.jl:4-63) over the same records, all in longdouble.  Returns float64 copies:
-    (means, covs) or (means, covs, smoothed means, smoothed covs, diffusions)."""
+def lorenz96_jac_ld(u):
+    """oracle _l96_jac, whose float64 work array would round the longdouble arguments."""
+    n = len(u)
+    J = np.zeros((n, n), dtype=np.longdouble)
+    for i in range(n):
+        ip, im2, im1 = (i + 1) % n, (i - 2) % n, (i - 1) % n
+        J[i, ip] += u[im1]
+        J[i, im2] -= u[im1]
+        J[i, im1] += u[ip] - u[im2]
+        J[i, i] -= 1
+    return J
+
+
+def jac_ld(vf, u, p):
+    """The field's Jacobian on longdouble arguments.  The oracle's own `vf.jac` where it builds the matrix from its arguments
+    (np.array of longdouble entries stays longdouble; parameters enter as their float64 values, so that 1.0 / c and the like are
+    the oracle's); restated where it rounds them into a float64 array (Pleiades, Lorenz-96)."""
+    if vf.name == "pleiades":
+        return pleiades_jac_ld(u)
+    if vf.name == "lorenz96":
+        return lorenz96_jac_ld(u)
+    J = np.asarray(vf.jac(u, p, 0.0))
+    assert J.dtype == np.longdouble or vf.name == "linear", (vf.name, J.dtype)  # linear: the constant diag(p), exact in float64
+    return J.astype(np.longdouble)
+
+
+def filter_ld(vf, u0, q, dt, nsteps, kind="EK1", with_smoother=False, diffusion="dynamic", tgrid=None, full=False):
+    """Any oracle vector field (`vf.f` is written for any scalar type, the Jacobian comes from jac_ld; the parameters are handed
+    over as their float64 values).  EK0 / EK1 filter and, if asked, the RTS pass (src/smoothing.jl:4-63) over the same records,
+    all in longdouble.  diffusion = "dynamic" (src/diffusions.jl:72-80), or "fixed" (src/diffusions.jl:11-36 in the static order of
+    src/perform_step.jl:56-63: the filter runs with sigma^2 = 1, the global diffusion is the running mean of z' S^-1 z / d, and the
+    postamble, src/integrator_utils.jl:4-18, rescales every covariance by the final one, which is also the diffusion of every
+    step of the RTS pass).  tgrid: the save times (float64; step n is the float64 difference tgrid[n+1] - tgrid[n], as on every
+    other side); without it nsteps steps of dt.  Returns float64 copies: (means, covs) or (means, covs, smoothed means, smoothed
+    covs, diffusions); full=True: a dict of those and the log-likelihood sum -(z' S^-1 z + log det S + d log 2 pi) / 2
+    (src/perform_step.jl:66; NaN for "fixed", src/integrator_utils.jl:6)."""
     ld = np.longdouble
     d, NB = vf.d, q + 1
     D = d * NB
+    p = vf.p
     coef = np.zeros((d, NB), dtype=ld)
     coef[:, 0] = np.asarray(u0, dtype=ld)
     for k in range(q):  # Taylor-mode initial state (src/state_initialization.jl:15-42) in longdouble
-        fu = vf.f([JetLD(coef[i].copy()) for i in range(d)], None, 0.0)
+        fu = vf.f([JetLD(coef[i].copy()) for i in range(d)], p, 0.0)
         for i in range(d):
             coef[i, k + 1] = JetLD.lift(fu[i], NB).c[k] / (k + 1)
     m = np.concatenate([coef[:, k] * ld(math.factorial(k)) for k in range(NB)])
@@ -242,33 +297,61 @@ def filter_ld(vf, u0, q, dt, nsteps, kind="EK1", with_smoother=False):
             v = ld(1) / (ld(2 * q + 1 - row - col) * ld(math.factorial(q - row)) * ld(math.factorial(q - col)))
             for i in range(d):
                 Q[row * d + i, col * d + i] = v
-    h = ld(dt)
-    P = np.repeat(np.array([h ** (ld(j) - ld(q) - ld(0.5)) for j in range(NB)], dtype=ld), d)
-    PI = ld(1) / P
+
+    def precond(h):
+        return np.repeat(np.array([h ** (ld(j) - ld(q) - ld(0.5)) for j in range(NB)], dtype=ld), d)
+
+    if tgrid is None:
+        hs = [ld(dt)] * nsteps
+    else:
+        assert len(tgrid) == nsteps + 1
+        hs = [ld(x) for x in np.diff(np.asarray(tgrid, np.float64))]
+    Ps = {}
+    for h in hs:
+        if float(h) not in Ps:
+            Ps[float(h)] = precond(h)
     S_ = np.zeros((D, D), dtype=ld)
     means, covs, diffs = [m.copy()], [S_.copy()], []
+    loglik, gdiff = ld(0), None
     for n in range(nsteps):
+        P = Ps[float(hs[n])]
+        PI = ld(1) / P
         mt, X = P * m, S_ * np.outer(P, P)
         mp_ = A @ mt
         up = (PI * mp_)[:d]
-        du = np.asarray(vf.f(list(up), None, 0.0), dtype=ld)
+        du = np.asarray(vf.f(list(up), p, 0.0), dtype=ld)
         z = (PI * mp_)[d:2 * d] - du
         H = np.zeros((d, D), dtype=ld)
         if kind == "EK1":
-            H[:, :d] = -pleiades_jac_ld(up) * PI[:d][None, :]
+            H[:, :d] = -jac_ld(vf, up, p) * PI[:d][None, :]
         H[:, d:2 * d] = np.diag(PI[d:2 * d])
-        W = H @ Q @ H.T
-        s2 = (z @ solve_spd_ld(W, z[:, None])[:, 0]) / d
-        Xp = A @ X @ A.T + s2 * Q
+        if diffusion == "dynamic":
+            W = H @ Q @ H.T
+            s2 = (z @ solve_spd_ld(W, z[:, None])[:, 0]) / d
+            Xp = A @ X @ A.T + s2 * Q
+        else:
+            assert diffusion == "fixed", diffusion
+            Xp = A @ X @ A.T + Q
         C = Xp @ H.T
         Sm = H @ C
         K = solve_spd_ld(Sm, C.T).T
+        if diffusion == "fixed":  # oracle perform_step: success_iter = number of accepted steps so far
+            dtn = (z @ solve_spd_ld(Sm, z[:, None])[:, 0]) / d
+            gdiff = dtn if n == 0 else gdiff + (dtn - gdiff) / n
+            s2 = gdiff
+        elif full:
+            Lc = chol_ld(Sm)
+            loglik += -(z @ solve_spd_ld(Sm, z[:, None])[:, 0] + 2 * np.sum(np.log(np.diag(Lc))) + d * np.log(2 * ld(np.pi))) / 2
         mf = mp_ - K @ z
         IKH = np.eye(D, dtype=ld) - K @ H
         Xf = IKH @ Xp @ IKH.T  # Joseph form (see lorenz_mp)
         Xf = (Xf + Xf.T) / 2
         m, S_ = PI * mf, Xf * np.outer(PI, PI)
         means.append(m.copy()); covs.append(S_.copy()); diffs.append(s2)
+    if diffusion == "fixed":  # postamble
+        covs = [c * gdiff for c in covs]
+        diffs = [gdiff for _ in diffs]
+        loglik = ld(np.nan)
     f64 = lambda a: np.array(a).astype(np.float64)  # noqa: E731
     if not with_smoother:
         return f64(means), f64(covs)
@@ -277,8 +360,10 @@ def filter_ld(vf, u0, q, dt, nsteps, kind="EK1", with_smoother=False):
     sm, sc = [None] * (nsteps + 1), [None] * (nsteps + 1)
     sm[nsteps], sc[nsteps] = means[nsteps], covs[nsteps]
     sm[0], sc[0] = means[0], covs[0]
-    PP = np.outer(P, P)
     for i in range(nsteps - 1, 0, -1):
+        P = Ps[float(hs[i])]
+        PI = ld(1) / P
+        PP = np.outer(P, P)
         mt, X = P * means[i], covs[i] * PP
         B = A @ X @ A.T + diffs[i] * Q
         B = (B + B.T) / 2
@@ -287,37 +372,126 @@ def filter_ld(vf, u0, q, dt, nsteps, kind="EK1", with_smoother=False):
         Ss = X + G @ (sc[i + 1] * PP - B) @ G.T
         Ss = (Ss + Ss.T) / 2
         sm[i], sc[i] = PI * ms_, Ss * np.outer(PI, PI)
+    if full:
+        return dict(mean_filt=f64(means), cov_filt=f64(covs), mean_smooth=f64(sm), cov_smooth=f64(sc), diffusions=f64(diffs),
+                    loglik=float(loglik))
     return f64(means), f64(covs), f64(sm), f64(sc), f64(diffs)
 
 
-def pleiades_fixture(q, kind, nsteps, dt, trajs=(0, 4)):
-    """Trajectories `trajs` of the Pleiades ensemble (positions perturbed by 1e-3): filter and smoother in
-    extended precision, and the float64 oracle's distance from them -- per derivative block for the means (all records) and
-    for the covariance at one record each: the LAST filter record and smoothed record 1 (the one the backward pass reaches
-    last), stored as packed lower triangles."""
-    vp = orc.vector_field("pleiades")
-    u0s = orc.ensemble_u0(vp.u0, max(trajs) + 1, 1e-3, n_perturbed=14)
-    D = 28 * (q + 1)
+def team_fixture(vf, u0s, trajs, q, kind, nsteps, dt, with_loglik=False):
+    """Trajectories `trajs` of the ensemble `u0s`: filter and smoother in extended precision, and the float64 oracle's distance
+    from them -- per derivative block for the means (all records) and for the covariance at one record each: the LAST filter
+    record and smoothed record 1 (the one the backward pass reaches last), stored as packed lower triangles."""
+    d = vf.d
+    D = d * (q + 1)
     il = np.tril_indices(D)
     out = dict(trajs=np.array(trajs), u0s=u0s[list(trajs)], dt=dt, nsteps=nsteps, order=q, ek1=int(kind == "EK1"),
                cov_record_filt=nsteps, cov_record_smooth=1)
     acc = {k: [] for k in ("mean_filt", "mean_smooth", "diffusions", "cov_filt_tril", "cov_smooth_tril", "oracle_block_err_filt",
                            "oracle_block_err_smooth", "oracle_cov_err_filt", "oracle_cov_err_smooth", "oracle_diffusion_err")}
+    if with_loglik:
+        acc["loglik"], acc["oracle_loglik_err"] = [], []
     for i in trajs:
-        mf, cf, ms, cs, df = filter_ld(vp, u0s[i], q, dt, nsteps, kind=kind, with_smoother=True)
-        sol = orc.solve(vp, orc.Alg(kind, q, "dynamic", True), u0=u0s[i], tspan=(0.0, nsteps * dt), dt=dt)
+        r = filter_ld(vf, u0s[i], q, dt, nsteps, kind=kind, with_smoother=True, full=True)
+        mf, cf, ms, cs, df = r["mean_filt"], r["cov_filt"], r["mean_smooth"], r["cov_smooth"], r["diffusions"]
+        sol = orc.solve(vf, orc.Alg(kind, q, "dynamic", True), u0=u0s[i], tspan=(0.0, nsteps * dt), dt=dt)
         acc["mean_filt"].append(mf); acc["mean_smooth"].append(ms); acc["diffusions"].append(df)
         acc["cov_filt_tril"].append(cf[nsteps][il]); acc["cov_smooth_tril"].append(cs[1][il])
-        acc["oracle_block_err_filt"].append(block_err(sol.means(smoothed=False), mf, 28))
-        acc["oracle_block_err_smooth"].append(block_err(sol.means(smoothed=True), ms, 28))
+        acc["oracle_block_err_filt"].append(block_err(sol.means(smoothed=False), mf, d))
+        acc["oracle_block_err_smooth"].append(block_err(sol.means(smoothed=True), ms, d))
         acc["oracle_cov_err_filt"].append(cov_err(sol.covs(smoothed=False)[nsteps:nsteps + 1], cf[nsteps:nsteps + 1]))
         acc["oracle_cov_err_smooth"].append(cov_err(sol.covs(smoothed=True)[1:2], cs[1:2]))
         acc["oracle_diffusion_err"].append(float(np.max(np.abs(sol.diffusions - df) / np.abs(df))))
+        if with_loglik:
+            acc["loglik"].append(r["loglik"])
+            acc["oracle_loglik_err"].append(abs(sol.log_likelihood - r["loglik"]) / abs(r["loglik"]))
     out.update({k: np.array(v) for k, v in acc.items()})
     return out
 
 
+def pleiades_fixture(q, kind, nsteps, dt, trajs=(0, 4)):
+    """Trajectories `trajs` of the Pleiades ensemble (positions perturbed by 1e-3), see team_fixture."""
+    vp = orc.vector_field("pleiades")
+    return team_fixture(vp, orc.ensemble_u0(vp.u0, max(trajs) + 1, 1e-3, n_perturbed=14), trajs, q, kind, nsteps, dt)
+
+
+def lorenz96_fixture(q, kind, nsteps=12, dt=2.0**-7, trajs=(0, 5)):
+    vf = orc.vector_field("lorenz96")
+    return team_fixture(vf, orc.ensemble_u0(vf.u0, 6, 1e-2), trajs, q, kind, nsteps, dt, with_loglik=True)
+
+
+ADMIT_DIFFUSION_ERR = 1e-4  # see the module docstring
+
+
+def small_fixture(rhs, kind, q, diffusion, dt, nsteps=SMALL_NSTEPS, ntraj=SMALL_NTRAJ):
+    """Trajectories 0 ... ntraj-1 of ensemble_u0(u0, ntraj, 1e-2) on the save times np.arange(nsteps + 1) * dt: filter and
+    smoother in extended precision with the covariances of EVERY record (packed lower triangles), the diffusions and the
+    log-likelihood; next to them the float64 oracle's distance from each, per trajectory."""
+    vf = orc.vector_field(rhs)
+    u0s = orc.ensemble_u0(vf.u0, ntraj, 1e-2)
+    tg = np.arange(nsteps + 1) * dt
+    D = vf.d * (q + 1)
+    il = np.tril_indices(D)
+    out = dict(rhs=rhs, kind=kind, order=q, ek1=int(kind == "EK1"), diffusionmodel=diffusion, dt=dt, nsteps=nsteps, t=tg,
+               trajs=np.arange(ntraj), u0s=u0s)
+    acc = {k: [] for k in ("mean_filt", "mean_smooth", "cov_filt_tril", "cov_smooth_tril", "diffusions", "loglik",
+                           "oracle_block_err_filt", "oracle_block_err_smooth", "oracle_cov_err_filt", "oracle_cov_err_smooth",
+                           "oracle_diffusion_err", "oracle_loglik_err")}
+    for i in range(ntraj):
+        r = filter_ld(vf, u0s[i], q, dt, nsteps, kind=kind, with_smoother=True, diffusion=diffusion, tgrid=tg, full=True)
+        sol = orc.solve(vf, orc.Alg(kind, q, diffusion, True), u0=u0s[i], tgrid=tg)
+        assert len(sol.t) == nsteps + 1 and sol.retcode == "Success"
+        for name, sm in (("filt", False), ("smooth", True)):
+            acc["mean_" + name].append(r["mean_" + name])
+            acc[f"cov_{name}_tril"].append(r["cov_" + name][:, il[0], il[1]])
+            acc["oracle_block_err_" + name].append(block_err(sol.means(smoothed=sm), r["mean_" + name], vf.d))
+            acc["oracle_cov_err_" + name].append(cov_err(sol.covs(smoothed=sm)[1:], r["cov_" + name][1:]))  # record 0: zero
+        acc["diffusions"].append(r["diffusions"]); acc["loglik"].append(r["loglik"])
+        acc["oracle_diffusion_err"].append(float(np.max(np.abs(np.asarray(sol.diffusions) - r["diffusions"]) / np.abs(r["diffusions"]))))
+        acc["oracle_loglik_err"].append(abs(sol.log_likelihood - r["loglik"]) / abs(r["loglik"]) if diffusion == "dynamic" else np.nan)
+    out.update({k: np.array(v) for k, v in acc.items()})
+    return out
+
+
+def admit(name, fx):
+    worst = float(np.max(fx["oracle_diffusion_err"]))
+    assert worst <= ADMIT_DIFFUSION_ERR, (f"{name}: the oracle's diffusions are {worst:.1e} relative off the extended-precision ones "
+                                          f"(> {ADMIT_DIFFUSION_ERR}): rounding noise, no yardstick -- pick another step size")
+
+
+def write_if_changed(path, fx):
+    """Leave a committed fixture alone when its contents are what was just computed."""
+    if os.path.exists(path):
+        old = np.load(path)
+        if sorted(old.files) == sorted(fx) and all(np.array_equal(old[k], np.asarray(fx[k]), equal_nan=np.asarray(fx[k]).dtype.kind == "f") for k in fx):
+            return False
+    np.savez_compressed(path, **fx)
+    return True
+
+
+def main_small():
+    for rhs, kind, q, diffusion, dt in SMALL_CASES:
+        name = small_name(rhs, kind, q, diffusion)
+        fx = small_fixture(rhs, kind, q, diffusion, dt)
+        admit(name, fx)
+        wrote = write_if_changed(os.path.join(HERE, name + ".npz"), fx)
+        print(name, "(written)" if wrote else "(unchanged)", ": oracle vs extended precision, filter blocks", fx["oracle_block_err_filt"].max(axis=0),
+              "cov", fx["oracle_cov_err_filt"].max(), "| smoother blocks", fx["oracle_block_err_smooth"].max(axis=0), "cov",
+              fx["oracle_cov_err_smooth"].max(), "| diffusions", fx["oracle_diffusion_err"].max(), "loglik", fx["oracle_loglik_err"].max(), flush=True)
+    for kind, q in LORENZ96_CASES:
+        name = lorenz96_name(kind, q)
+        fx = lorenz96_fixture(q, kind)
+        admit(name, fx)
+        wrote = write_if_changed(os.path.join(HERE, name + ".npz"), fx)
+        print(name, "(written)" if wrote else "(unchanged)", ": oracle vs extended precision, filter blocks", fx["oracle_block_err_filt"].max(axis=0),
+              "cov", fx["oracle_cov_err_filt"], "| smoother blocks", fx["oracle_block_err_smooth"].max(axis=0), "cov", fx["oracle_cov_err_smooth"],
+              "| diffusions", fx["oracle_diffusion_err"], "loglik", fx["oracle_loglik_err"], flush=True)
+
+
 if __name__ == "__main__":
+    if "--small" in sys.argv[1:]:
+        main_small()
+        sys.exit(0)
     vf = orc.vector_field("lorenz63")
     u0 = orc.ensemble_u0(vf.u0, 1, 1e-2)[0]
     dt, ns = 2.0**-9, 1024

@@ -22,9 +22,9 @@ def _alg(pkg, kind, order, diffusion="dynamic", smooth=True):
 GOLDEN_FIXED = ["fhn_ek0_q1_cfg1", "lorenz_ek1_q3", "lv_ek1_q2_fixeddiff", "lv_ek0_q4", "vdp_ek1_q5"]
 
 
-# The fixed-step filter has a second, experimental mapping for D <= 16 (csrc/filter_rows.h, 16 lanes per trajectory; off by
-# default: it measured no faster than the lane filter); ODEF_FILTER_ROWS_MAX_N is read at every launch and
-# selects it for ensembles below that size.
+# The fixed-step filter has a second mapping for D <= 16 (csrc/rows_filter.h, 16 lanes per trajectory), the default below
+# 12 288 trajectories (kFilterRowsMaxN, csrc/rows_launch.h); ODEF_FILTER_ROWS_MAX_N is read at every launch and overrides that
+# size: 0 forces the lane filter, a huge value the row-team filter.
 FILTER_KERNELS = {"lane": "0", "rows": "1000000000"}
 
 

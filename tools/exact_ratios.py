@@ -1,11 +1,59 @@
 #!/usr/bin/env python3
-"""How far the D = 84 / 112 / 168 kernels are from the extended-precision evaluation of the reference algorithm, in units of the
+"""Without arguments: how far the D = 84 / 112 / 168 kernels are from the extended-precision evaluation of the reference algorithm, in units of the
 float64 oracle's own distance (tests/golden/exact_pleiades_*_smooth_ld.npz, generator tests/golden/make_exact.py): one JSON line
-per fixture and kernel combination -- the numbers behind the factor-16 bar of tests/_parity.py check_against_exact_fixture."""
+per fixture and kernel combination -- the numbers behind the factor-16 bar of tests/_parity.py check_against_exact_fixture.
+
+--small: the same for the small-state kernels and for Lorenz-96 on the matrix-core kernels (tests/golden/exact_small_*_ld.npz,
+exact_lorenz96_*_smooth_ld.npz): every kernel family the launchers can select, through the C ABI as tests/test_gpu_exact.py runs
+them; ratios are error / max(oracle's distance, n_steps 2^-52), the largest over the checked trajectories
+(check_against_exact_floored).  --small-emul: the host build of the device source instead (tests/test_exact_emul.py; no GPU).
+Each line carries "source": "device" or "emulation" and the oracle's distances the ratios are measured in."""
 import json, os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
+
+
+def small_lines(source):
+    import _exact_cases as X
+
+    def emit(fixture, kernels, fx, run):
+        out = {"fixture": fixture, "kernels": kernels, "source": source, "oracle_distance": X.oracle_distance(fx)}
+        try:
+            out.update(X.worst_of([X.ratio_record(r) for r in run()]))
+        except AssertionError as e:  # a ratio above the bar: the message carries the figures
+            out["failed"] = str(e).splitlines()[0]
+        print(json.dumps(out), flush=True)
+
+    if source == "emulation":
+        import test_exact_emul as T
+
+        for case in X.SMALL_CASES:
+            fx = X.load(X.small_name(*case[:4]))
+            D = X.SMALL_DIM[case[0]] * (case[2] + 1)
+            emit(X.case_id(case), "lane+" + ("lane" if D <= 12 else "rows"), fx, lambda: T.check_emulation(case, "lane"))
+            if D <= 16:
+                emit(X.case_id(case), "rows+bcast", fx, lambda: T.check_emulation(case, "rows"))
+        return
+    import odefilters_jl_amd as pkg
+    import test_gpu_exact as G
+
+    def setenv(k, v):
+        os.environ[k] = v
+
+    for case, filt, smoother in G.COMBOS:
+        fx, sol = G.solve_small(pkg, case, filt, smoother, setenv)
+        emit(X.case_id(case), f"{filt}+{smoother}", fx, lambda: G.check_small(fx, sol, case, filt, smoother))
+    for kind, q in X.LORENZ96_CASES:
+        for smoother in ("split", "persistent"):
+            fx, sol = G.solve_lorenz96(pkg, kind, q, smoother, setenv)
+            emit(f"lorenz96-{kind}{q}", f"mfma+{smoother}", fx, lambda: G.check_lorenz96(fx, sol, kind, q, smoother))
+
+
+if "--small" in sys.argv[1:] or "--small-emul" in sys.argv[1:]:
+    small_lines("emulation" if "--small-emul" in sys.argv[1:] else "device")
+    sys.exit(0)
+
 import odefilters_jl_amd as pkg
 import odefilter_oracle as orc
 import _parity as P
