@@ -37,6 +37,8 @@
  *   odef_errors_field ids           sol.errors, sol.u_analytic                    src/solution.jl:10-11,68-74,129-130
  *   odef_data_field ids             nothing in this version of the reference (later ones ship it as fenrir_data_loglik): the
  *                                   marginal log-likelihood of noisy observations under the posterior, per trajectory
+ *   odef_event_field ids            nothing in the reference itself: what a ContinuousCallback with the condition u[c] - level
+ *                                   answers in the SciML interface it plugs into, asked of the finished posterior
  *   odef_summary_field ids          nothing in the reference: per-time mean and covariance of the ensemble's Gaussian mixture,
  *                                   reduced on the device and read with odef_get (see odef_summary_field)
  *   odef_group_* / odef_allgather   nothing in the reference (it has no ensemble and no distributed code):
@@ -142,26 +144,28 @@ typedef enum {
   ODEF_F_COUNT_
 } odef_field;
 
-/* Derived outputs and their caches.  Three families of fields are computed from the records on the device when first asked for --
- * the ensemble summary (odef_summary_field), the solution errors (odef_errors_field) and the data log-likelihood
- * (odef_data_field) -- and cached; odef_field_bytes, odef_get and odef_get_device serve them like any other field.  One rule says
- * when a cached result is dropped, so that the next request computes it again.  The context tracks six things that can change:
+/* Derived outputs and their caches.  Four families of fields are computed from the records on the device when first asked for --
+ * the ensemble summary (odef_summary_field), the solution errors (odef_errors_field), the data log-likelihood
+ * (odef_data_field) and the event times (odef_event_field) -- and cached; odef_field_bytes, odef_get and odef_get_device serve them like any other field.  One rule says
+ * when a cached result is dropped, so that the next request computes it again.  The context tracks seven things that can change:
  *   the filter records    MEAN, COV_TRIL, DIFFUSION, T                 source 0
  *   the smoothed records  SMOOTH_MEAN, SMOOTH_COV_TRIL                 source 1
  *   the dense records     DENSE_MEAN, DENSE_COV_TRIL                   source 2
  *   the problem           u0, p, t0
  *   the bound truth       ODEF_E_REFERENCE
  *   the observations      ODEF_L_OBS_SAVE / COMPONENT / VALUE / NOISE
+ *   the event spec        ODEF_EV_SPEC / ODEF_EV_LEVEL
  * and what is derived from what:
  *   the summary of source k       its record set; a new problem drops it as well
  *   the errors of source k        its record set, the bound truth, the problem
  *   the data log-likelihood       the filter records, the observations, the problem
+ *   the events of source k        its record set, the filter records (both sources predict from them), the event spec, the problem
  *   the filter records that odef_solve_fixed leaves staged for odef_smooth (the workgroup-per-trajectory path)   the filter records
  * A record set changes when an entry point writes it -- odef_solve_* all three (every summary includes its trajectories by the
  * RETCODE of the solve), odef_smooth the smoothed, odef_dense_output / odef_dense_sample the dense records -- and when the caller
  * may: odef_bind_device of one of its fields replaces the buffer, and odef_get_device of one hands out a WRITABLE pointer, so both
  * count as a change of the whole set.  odef_set_problem* change the problem, a bind of ODEF_E_REFERENCE the truth, a bind of an
- * ODEF_L_OBS_* the observations.  odef_get, the host copy, changes nothing.  Records edited through a pointer taken EARLIER are not
+ * ODEF_L_OBS_* the observations, a bind of ODEF_EV_SPEC or ODEF_EV_LEVEL the event spec.  odef_get, the host copy, changes nothing.  Records edited through a pointer taken EARLIER are not
  * seen: take the pointer again (or bind) after writing. */
 
 /* Ensemble summary per time, reduced on the device (nothing in the reference: it has no ensemble).  For one time and the n
@@ -273,6 +277,66 @@ typedef enum {
   ODEF_L_OBS_VALUE = 202,     /* odef_bind_device only */
   ODEF_L_OBS_NOISE = 203      /* odef_bind_device only */
 } odef_data_field;
+
+/* Event location per trajectory, on the device: the times at which component c of the posterior mean crosses a level -- what a
+ * ContinuousCallback with the condition u[c] - level answers in a SciML-style solver, here asked of the finished posterior (the solve
+ * is not stopped and the state not modified).  Per trajectory i over its own saves t_0 .. t_{n-1} (n = odef_n_save on a fixed grid,
+ * NSAVED[i] after an adaptive solve), with g_k = m_c[k] - level_i, m the mean record of the source:
+ *   bracket   an interval k -> k + 1 with t_{k+1} > t_k is an UP bracket if g_k < 0 && g_{k+1} >= 0, a DOWN bracket if g_k > 0 &&
+ *             g_{k+1} <= 0; direction +1 / -1 keeps the up / down brackets, 0 both.  A zero-length interval (a repeated tstop, the
+ *             repeat of a rejected attempt) holds no event; a NaN (record or level) makes every comparison false: no event; g_0 == 0
+ *             is not an event.  A crossing that does not show at the two ends of a step (a double root inside one step) is NOT
+ *             detected.  A trajectory whose RETCODE is not Success is scanned over the records it has.
+ *   COUNT     the brackets of the whole trajectory (may exceed K); the first min(COUNT, K) in time order are located
+ *   root      g_{k+1} == 0: t* = t_{k+1}, every output is the stored record, NEVAL = 0.  Otherwise the root in (t_k, t_{k+1}) of
+ *             E[u_c(t)] - level_i under the source's dense posterior (the semantics of odef_dense_output), by bracketed Newton with
+ *             the slope E[u'_c(t)], entry d + c of the same evaluation: start at the secant point of the bracket's ends, shrink the
+ *             bracket by the sign of g after each evaluation, replace an iterate outside the closed bracket (or a zero / non-finite
+ *             slope) by the midpoint, stop at g == 0 or a step of at most 2^-40 (t_{k+1} - t_k); at most 64 evaluations, at the cap
+ *             the current iterate is returned.  The outputs are one dense evaluation at t*.  Source 0 only: the filter's dense mean on
+ *             (t_k, t_{k+1}) is the prediction from save k and jumps at t_{k+1} by the measurement update, so a bracket of the stored
+ *             means may hold no root.  The first evaluation is therefore the left limit at t_{k+1}; if it has not passed the level
+ *             the crossing lies inside the update: t* = t_{k+1}, every output is the stored record, NEVAL = 1.  (The smoothed
+ *             interpolant is continuous at the saves.)
+ * Field id = ODEF_EV_BASE + 8 * source + quantity, source 0: the filter posterior, 1: the smoothed posterior; slot s of K:
+ *   COUNT      int32  [N]
+ *   TIME       double [K][N]      t*
+ *   TIME_VAR   double [K][N]      Var u_c(t*) / (E u'_c(t*))^2, the first-order variance of the event time (plain IEEE: zero slope -> inf)
+ *   U          double [K][d][N]   E[u(t*)]
+ *   DIRECTION  int32  [K][N]      +1 up, -1 down
+ *   SAVE       int32  [K][N]      k, the left save of the bracket (a raw record index after an adaptive solve)
+ *   NEVAL      int32  [K][N]      dense evaluations spent (distinct times, the one at t* included)
+ * Unused slots hold NaN in the doubles, 0 in DIRECTION and NEVAL, -1 in SAVE.  odef_field_bytes, odef_get and odef_get_device accept
+ * these ids.  Inputs, device memory bound with odef_bind_device (read only, never written; NULL lets one go):
+ *   ODEF_EV_SPEC   int64  [3]          {component c, direction, K}
+ *   ODEF_EV_LEVEL  double [1] or [N]   shared, or per trajectory (told by the byte count, as for p)
+ * The first request for a source copies the three spec words to the host, validates them, runs the pass on the context's stream
+ * (two launches: a scan of row c of the mean records, then the refinement, one lane per trajectory and slot) and caches all outputs
+ * of that source (dropped as "Derived outputs and their caches" above says); two requests agree bit for bit.  Refused with a
+ * message: before a solve; source 1 before odef_smooth; a context that kept only the final state; the MV diffusion models; a (d, q)
+ * without a kernel (built for d <= 4, q <= 5, d (q + 1) <= 12); an input missing; ODEF_EV_SPEC not 24 bytes; a level of neither 8
+ * nor 8 N bytes; a component outside 0 .. d - 1; a direction outside {-1, 0, 1}; K < 1, K > 65535, or K N max(d, 1) 8 bytes at or
+ * above 2 GiB.  odef_kernel_time_ms / odef_kernel_name report the last pass as which = 5; its n_launches counts the launches since
+ * the context was created (a request served from the cache leaves it unchanged). */
+typedef enum {
+  ODEF_EV_BASE = 256,
+  ODEF_EV_COUNT = 256,
+  ODEF_EV_TIME = 257,
+  ODEF_EV_TIME_VAR = 258,
+  ODEF_EV_U = 259,
+  ODEF_EV_DIRECTION = 260,
+  ODEF_EV_SAVE = 261,
+  ODEF_EV_NEVAL = 262,
+  ODEF_EV_SMOOTH_COUNT = 264,
+  ODEF_EV_SMOOTH_TIME = 265,
+  ODEF_EV_SMOOTH_TIME_VAR = 266,
+  ODEF_EV_SMOOTH_U = 267,
+  ODEF_EV_SMOOTH_DIRECTION = 268,
+  ODEF_EV_SMOOTH_SAVE = 269,
+  ODEF_EV_SMOOTH_NEVAL = 270,
+  ODEF_EV_SPEC = 280, /* odef_bind_device only */
+  ODEF_EV_LEVEL = 281 /* odef_bind_device only */
+} odef_event_field;
 
 /* POD mirror of the reference's keyword structs (src/algorithms.jl:23-28,46-51) plus the
  * ensemble shape.  Zero-initialise, set struct_size = sizeof(odef_config). */
@@ -407,7 +471,7 @@ int odef_bind_device(odef_ctx* ctx, int field, void* dev_ptr, size_t bytes);
 int odef_synchronize(odef_ctx* ctx);
 
 /* Device time of the last filter (which=0) / smoother (which=1) / ensemble-summary (which=2) / solution-error (which=3) /
- * data-likelihood (which=4) launch, measured with
+ * data-likelihood (which=4) / event-location (which=5) launch, measured with
  * hipEvents on the launch stream; n_launches = kernels launched by that call. */
 int odef_kernel_time_ms(odef_ctx* ctx, int which, float* ms, int* n_launches);
 /* Name of the kernel that call launched (the dominant one of a multi-kernel pass), as a profiler prints it, e.g.

@@ -72,6 +72,25 @@ const L_OBS_SAVE = 200
 const L_OBS_COMPONENT = 201
 const L_OBS_VALUE = 202
 const L_OBS_NOISE = 203
+# event location per trajectory (odef_event_field, include/odefilter.h): id = EV_BASE + 8 * source + quantity, two inputs that
+# odef_bind_device alone takes.  UNTESTED like the rest of this file.
+const EV_BASE = 256
+const EV_COUNT = 256
+const EV_TIME = 257
+const EV_TIME_VAR = 258
+const EV_U = 259
+const EV_DIRECTION = 260
+const EV_SAVE = 261
+const EV_NEVAL = 262
+const EV_SMOOTH_COUNT = 264
+const EV_SMOOTH_TIME = 265
+const EV_SMOOTH_TIME_VAR = 266
+const EV_SMOOTH_U = 267
+const EV_SMOOTH_DIRECTION = 268
+const EV_SMOOTH_SAVE = 269
+const EV_SMOOTH_NEVAL = 270
+const EV_SPEC = 280
+const EV_LEVEL = 281
 const RETCODES = (:Success, :MaxIters, :DtLessThanMin, :Unstable, :Unstable)
 
 """Ensemble algorithm: all trajectories of an `EnsembleProblem` on one GPU (`devices` empty / one entry) or sharded
@@ -86,7 +105,7 @@ end
 EnsembleHIP(rhs::Symbol; device=-1, devices=Int32[]) = EnsembleHIP(device, rhs, collect(Int32, devices))
 
 lasterr(ctx) = unsafe_string(ccall((:odef_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx))
-# which kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) pass launched, and its device time in ms
+# which kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) / data-likelihood (4) / event-location (5) pass launched, and its device time in ms
 function kernel_name(ctx, which::Integer)
     buf = zeros(UInt8, 256)
     GC.@preserve buf ccall((:odef_kernel_name, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{UInt8}, Csize_t), ctx, which, buf, length(buf))
@@ -152,6 +171,27 @@ function data_loglik(ctx, n_traj::Integer, saves, comps, values, noise)
         check(ccall((:odef_bind_device, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Csize_t), ctx, f, ptr, bytes), ctx)
     end
     return fetch(ctx, L_DATA_LOGLIK, Float64, n_traj), fetch(ctx, L_DATA_MAHALANOBIS, Float64, n_traj)
+end
+
+"""
+    events(ctx, n_traj, d, K, spec, level; source=0) -> (count, t, t_std, u, direction, save, neval)
+
+Level crossings of one component of the posterior mean per trajectory of the live context `ctx` -- what a `ContinuousCallback` with
+the condition `u[c] - level` answers, asked of the finished posterior --, located on the device by a scan of the records and
+bracketed Newton on the dense posterior (the state carries u', so the slope costs nothing).  `spec` and `level` are DEVICE pointers
+that stay the caller's, each given as `(ptr, bytes)`: `spec` Int64 [3] `{component (0-based), direction (-1, 0, +1), K}`, `level`
+Float64 [1] or [N].  `count[i]` counts all crossings, the first `K` are located: `t[i, s]`, `t_std[i, s]`, `u[:, i, s]`; unused
+slots hold NaN, direction 0, save -1.  source 0: filter posterior, 1: smoothed.  UNTESTED.
+"""
+function events(ctx, n_traj::Integer, d::Integer, K::Integer, spec, level; source::Integer=0)
+    for (f, (ptr, bytes)) in ((EV_SPEC, spec), (EV_LEVEL, level))
+        check(ccall((:odef_bind_device, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Csize_t), ctx, f, ptr, bytes), ctx)
+    end
+    id(q) = EV_BASE + 8 * source + q
+    count = fetch(ctx, id(0), Int32, n_traj)
+    t = fetch(ctx, id(1), Float64, n_traj, K)
+    return (count = count, t = t, t_std = sqrt.(fetch(ctx, id(2), Float64, n_traj, K)), u = permutedims(fetch(ctx, id(3), Float64, n_traj, d, K), (2, 1, 3)),
+            direction = fetch(ctx, id(4), Int32, n_traj, K), save = fetch(ctx, id(5), Int32, n_traj, K), neval = fetch(ctx, id(6), Int32, n_traj, K))
 end
 
 """

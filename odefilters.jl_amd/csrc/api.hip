@@ -20,6 +20,7 @@
 #include "summary.h"
 #include "errors.h"
 #include "datalik.h"
+#include "events.h"
 
 using namespace odef;
 
@@ -39,7 +40,7 @@ struct RhsInfo { int d, np; };
 const RhsInfo kRhs[] = {{2, 3}, {3, 3}, {2, 4}, {2, 1}, {2, 2}, {28, 0}, {16, 1}, {2, 3}};
 
 // the passes a context times and names: `which` of odef_kernel_time_ms / odef_kernel_name
-enum Pass { kPassFilter = 0, kPassSmooth = 1, kPassSummary = 2, kPassErrors = 3, kPassDataLik = 4, kPassCount };
+enum Pass { kPassFilter = 0, kPassSmooth = 1, kPassSummary = 2, kPassErrors = 3, kPassDataLik = 4, kPassEvents = 5, kPassCount };
 
 }  // namespace
 
@@ -87,6 +88,8 @@ struct odef_ctx {
   size_t err_ref_bytes = 0;
   DataLikState datalik;  // cached data log-likelihood of the filter records (odef_data_field)
   Buf obs[4];            // ODEF_L_OBS_SAVE / COMPONENT / VALUE / NOISE: caller memory, read only
+  EventsState events;    // cached event times of the filter and smoothed posterior (odef_event_field)
+  Buf evin[2];           // ODEF_EV_SPEC / ODEF_EV_LEVEL: caller memory, read only
   // odef_group runs its shards concurrently: with `defer` set, odef_solve_* / odef_smooth return after the launch and
   // complete_pending() does the wait + timing (pending: 1 = filter, 2 = smoother)
   bool defer = false;
@@ -266,6 +269,7 @@ enum : unsigned {
   kProblem = 1u << 3,       // u0, p, t0
   kTruth = 1u << 4,         // ODEF_E_REFERENCE
   kObservations = 1u << 5,  // ODEF_L_OBS_*
+  kEventSpec = 1u << 6,     // ODEF_EV_SPEC, ODEF_EV_LEVEL
 };
 
 // the record set an ODEF_F_* id belongs to (0: none)
@@ -289,18 +293,21 @@ void records_changed(odef_ctx* c, unsigned what) {
     if (what & (kFilterRecs << k | kTruth | kProblem)) c->errors.src[k].valid = c->errors.src[k].truth_valid = false;
   // data likelihood: the filter records, the observations, the problem
   if (what & (kFilterRecs | kObservations | kProblem)) c->datalik.valid = false;
+  for (int k = 0; k < 2; ++k)  // events of source k: record set k, the filter records (both sources predict from them), spec, problem
+    if (what & (kFilterRecs << k | kFilterRecs | kEventSpec | kProblem)) c->events.src[k].valid = false;
   // The filter records resident in the stage: the filter records.  odef_smooth works in the stage and leaves the smoothed records
   // (or another block layout) there, so new smoothed records end the residency as well.
   if (what & (kFilterRecs | kSmoothRecs)) c->stage_filter_recs = 0;
 }
 
-// One family of derived outputs (odef_summary_field / odef_errors_field / odef_data_field).  `check` touches no device; `fetch`
+// One family of derived outputs (odef_summary_field / odef_errors_field / odef_data_field / odef_event_field).  `check` touches no device; `fetch`
 // runs after it and returns the cached device array, running the pass first when the cache is stale.
 struct DerivedFamily {
   bool (*owns)(int field);
   int (*check)(const odef_ctx* c, int field, const char* who);  // 0, or -1 with the reason in odef_last_error
   size_t (*bytes)(const odef_ctx* c, int field);
   int (*fetch)(odef_ctx* c, int field, const char* who, void** ptr);
+  bool bytes_after_fetch = false;  // the byte count follows from an input in device memory: odef_field_bytes runs the pass as well
 };
 
 // odef_summary_field: id = ODEF_S_BASE + 8 source + quantity
@@ -493,10 +500,96 @@ int datalik_fetch(odef_ctx* c, int field, const char* who, void** ptr) {
   return 0;
 }
 
+// odef_event_field: id = ODEF_EV_BASE + 8 source + quantity, and the two inputs that odef_bind_device alone takes
+bool is_event_output(int field) {
+  return field >= ODEF_EV_BASE && field < ODEF_EV_BASE + 8 * 2 && (field - ODEF_EV_BASE) % 8 <= ODEF_EV_NEVAL - ODEF_EV_BASE;
+}
+bool is_event_input(int field) { return field == ODEF_EV_SPEC || field == ODEF_EV_LEVEL; }
+
+int events_check(const odef_ctx* c, int field, const char* who) {
+  const int source = (field - ODEF_EV_BASE) / 8;
+  if (!c->solved) return fail(c, "%s: event location requested before a solve (call odef_solve_* first)", who);
+  if (source == 1 && !c->smoothed_done) return fail(c, "%s: event location on the smoothed posterior needs odef_smooth first", who);
+  if (c->cfg.save_mode != ODEF_SAVE_EVERYSTEP || c->n_save < 2)
+    return fail(c, "%s: event location needs the records of every step, this context kept only the final state "
+                   "(ODEF_SAVE_EVERYSTEP)", who);
+  if (is_mv(c->cfg.diffusion))
+    return fail(c, "%s: event location is built for the scalar diffusion models, not :dynamicMV / :fixedMV", who);
+  if (!events_has(c->d, c->q))
+    return fail(c, "%s: event location has no kernel for (d, q) = (%d, %d); built for d <= 4, q <= 5, d (q + 1) <= 12", who, c->d, c->q);
+  static const char* const kName[2] = {"ODEF_EV_SPEC", "ODEF_EV_LEVEL"};
+  for (int k = 0; k < 2; ++k)
+    if (!c->evin[k].ptr) return fail(c, "%s: event location input missing: bind %s with odef_bind_device", who, kName[k]);
+  if (c->evin[0].bytes != 24)
+    return fail(c, "%s: event location: ODEF_EV_SPEC holds %zu bytes, it is [3] int64 {component, direction, K} = 24", who,
+                c->evin[0].bytes);
+  if (c->evin[1].bytes != 8 && c->evin[1].bytes != (size_t)c->cfg.n_traj * 8)
+    return fail(c, "%s: event location: ODEF_EV_LEVEL holds %zu bytes, it is one double (8) or one per trajectory (%zu)", who,
+                c->evin[1].bytes, (size_t)c->cfg.n_traj * 8);
+  return 0;
+}
+
+// runs the pass of a source when its cache is stale (the byte counts of all but COUNT depend on K, which the pass validates)
+int events_ensure(odef_ctx* c, int source, const char* who) {
+  EventsCache& ec = c->events.src[source];
+  if (ec.valid) return 0;
+  EventsRequest r;
+  std::memset(&r, 0, sizeof r);
+  r.pc = &c->pc;
+  r.N = c->cfg.n_traj;
+  r.n_save = c->n_save;
+  r.d = c->d;
+  r.q = c->q;
+  r.adaptive = c->adaptive;
+  r.source = source;
+  r.tgrid = c->d_tgrid;
+  r.tsave = (const double*)c->f[ODEF_F_T].ptr;
+  r.nsaved = (const int*)c->f[ODEF_F_NSAVED].ptr;
+  r.mean = (const double*)c->f[ODEF_F_MEAN].ptr;
+  r.cov = (const double*)c->f[ODEF_F_COV_TRIL].ptr;
+  r.diff = (const double*)c->f[ODEF_F_DIFFUSION].ptr;
+  r.smean = (const double*)c->f[ODEF_F_SMOOTH_MEAN].ptr;
+  r.scov = (const double*)c->f[ODEF_F_SMOOTH_COV_TRIL].ptr;
+  if (!r.mean || !r.cov || !r.diff || (c->adaptive ? !r.tsave || !r.nsaved : !r.tgrid) || (source == 1 && (!r.smean || !r.scov)))
+    return fail(c, "%s: the records of event source %d hold no data", who, source);
+  r.spec = c->evin[0].ptr;
+  r.level = (const double*)c->evin[1].ptr;
+  r.spec_bytes = c->evin[0].bytes;
+  r.level_bytes = c->evin[1].bytes;
+  std::string err;
+  if (set_device(c)) return -1;
+  if (events_run(c->events, ec, r, c->stream, &c->ms[kPassEvents], &c->nl[kPassEvents], c->kname[kPassEvents],
+                 sizeof c->kname[kPassEvents], err))
+    return fail(c, "%s: %s", who, err.c_str());
+  return 0;
+}
+
+int events_fetch(odef_ctx* c, int field, const char* who, void** ptr) {
+  const int source = (field - ODEF_EV_BASE) / 8, quantity = (field - ODEF_EV_BASE) % 8;
+  if (events_ensure(c, source, who)) return -1;
+  const EventsCache& ec = c->events.src[source];
+  void* const p[7] = {ec.count, ec.time, ec.tvar, ec.u, ec.direction, ec.save, ec.neval};
+  *ptr = p[quantity];
+  return 0;
+}
+
+// (K lives in device memory and is known once the pass has run: called after events_fetch only)
+size_t events_bytes(const odef_ctx* c, int field) {
+  const int source = (field - ODEF_EV_BASE) / 8, quantity = (field - ODEF_EV_BASE) % 8;
+  const size_t N = (size_t)c->cfg.n_traj, K = (size_t)c->events.src[source].K;
+  switch (quantity) {
+    case 0: return N * sizeof(int32_t);
+    case 1: case 2: return K * N * sizeof(double);
+    case 3: return K * (size_t)c->d * N * sizeof(double);
+    default: return K * N * sizeof(int32_t);
+  }
+}
+
 const DerivedFamily kDerived[] = {
     {is_summary_field, summary_check, summary_bytes, summary_fetch},
     {is_errors_field, errors_check, errors_bytes, errors_fetch},
     {is_datalik_output, datalik_check, datalik_bytes, datalik_fetch},
+    {is_event_output, events_check, events_bytes, events_fetch, true},
 };
 
 // the family that owns a field id, or nullptr: an ODEF_F_* buffer, a bind-only id, or no id at all
@@ -722,6 +815,7 @@ void odef_destroy(odef_ctx* c) {
   summary_free(c->summary);
   errors_free(c->errors);
   datalik_free(c->datalik);
+  events_free(c->events);
   for (int k = 0; k < 4; ++k)
     if (c->ev[k]) (void)hipEventDestroy(c->ev[k]);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1216,6 +1310,10 @@ int64_t odef_n_save(const odef_ctx* c) { return c ? c->n_save : -1; }
 int odef_field_bytes(const odef_ctx* c, int field, size_t* bytes) {
   if (!c || !bytes) return -1;
   if (const DerivedFamily* fam = derived_family(field)) {
+    if (fam->bytes_after_fetch) {  // (the context is the caller's own object; the pass fills its cache)
+      void* unused = nullptr;
+      return derived_fetch(const_cast<odef_ctx*>(c), fam, field, "odef_field_bytes", &unused, bytes);
+    }
     if (fam->check(c, field, "odef_field_bytes")) return -1;
     *bytes = fam->bytes(c, field);
     return 0;
@@ -1283,6 +1381,17 @@ int odef_bind_device(odef_ctx* c, int field, void* dev_ptr, size_t bytes) {
       b.bound = true;
     }
     records_changed(c, kObservations);
+    return 0;
+  }
+  if (is_event_input(field)) {  // the spec and the level of the event location: caller memory, read only; NULL lets it go
+    Buf& b = c->evin[field - ODEF_EV_SPEC];
+    b = Buf{};
+    if (dev_ptr) {
+      b.ptr = dev_ptr;
+      b.bytes = bytes;
+      b.bound = true;
+    }
+    records_changed(c, kEventSpec);
     return 0;
   }
   if (field < 0 || field >= ODEF_F_COUNT_ || field == ODEF_F_U0) return fail(c, "odef_bind_device: field %d cannot be bound", field);

@@ -99,6 +99,33 @@ DATA_FIELDS = {
 }
 K_DATA_LOGLIK = 4  # `which` of odef_kernel_time_ms / odef_kernel_name
 
+# event location per trajectory (odef_event_field, include/odefilter.h): id = EV_BASE + 8 * source + quantity
+EV_BASE = 256
+EV_SOURCE_FILTER, EV_SOURCE_SMOOTH = 0, 1
+EV_COUNT, EV_TIME, EV_TIME_VAR, EV_U, EV_DIRECTION, EV_SAVE, EV_NEVAL = range(7)
+EV_SPEC, EV_LEVEL = 280, 281  # odef_bind_device only
+EVENT_FIELDS = {
+    "ODEF_EV_BASE": 256,
+    "ODEF_EV_COUNT": 256, "ODEF_EV_TIME": 257, "ODEF_EV_TIME_VAR": 258, "ODEF_EV_U": 259, "ODEF_EV_DIRECTION": 260,
+    "ODEF_EV_SAVE": 261, "ODEF_EV_NEVAL": 262,
+    "ODEF_EV_SMOOTH_COUNT": 264, "ODEF_EV_SMOOTH_TIME": 265, "ODEF_EV_SMOOTH_TIME_VAR": 266, "ODEF_EV_SMOOTH_U": 267,
+    "ODEF_EV_SMOOTH_DIRECTION": 268, "ODEF_EV_SMOOTH_SAVE": 269, "ODEF_EV_SMOOTH_NEVAL": 270,
+    "ODEF_EV_SPEC": 280, "ODEF_EV_LEVEL": 281,
+}
+K_EVENTS = 5  # `which` of odef_kernel_time_ms / odef_kernel_name
+
+
+def event_field(source: int, quantity: int) -> int:
+    """Field id of an event array: source 0 filter / 1 smoothed posterior, quantity 0 COUNT / 1 TIME / 2 TIME_VAR / 3 U /
+    4 DIRECTION / 5 SAVE / 6 NEVAL."""
+    if source not in (0, 1) or quantity not in range(7):
+        raise OdefError(f"no event field for source {source}, quantity {quantity}")
+    return EV_BASE + 8 * source + quantity
+
+
+def _is_event_field(f: int) -> bool:
+    return EV_BASE <= f < EV_BASE + 16 and (f - EV_BASE) % 8 < 7
+
 # dtype and shape (of a Context `c`) of every derived field, by family and quantity; the source does not matter
 _FLAT = lambda c: (-1,)  # noqa: E731  ([n_t] counts, [N] per-trajectory values)
 _DERIVED_LAYOUT = {
@@ -111,10 +138,16 @@ _DERIVED_LAYOUT = {
     ("errors", E_NUSED): (np.int64, _FLAT),
     ("errors", E_U_ANALYTIC): (np.float64, lambda c: (-1, c.d, c.N)),
     ("data", L_DATA_LOGLIK - L_BASE): (np.float64, _FLAT), ("data", L_DATA_MAHALANOBIS - L_BASE): (np.float64, _FLAT),
+    ("event", EV_COUNT): (np.int32, _FLAT),
+    ("event", EV_TIME): (np.float64, lambda c: (-1, c.N)), ("event", EV_TIME_VAR): (np.float64, lambda c: (-1, c.N)),
+    ("event", EV_U): (np.float64, lambda c: (-1, c.d, c.N)),
+    ("event", EV_DIRECTION): (np.int32, lambda c: (-1, c.N)), ("event", EV_SAVE): (np.int32, lambda c: (-1, c.N)),
+    ("event", EV_NEVAL): (np.int32, lambda c: (-1, c.N)),
 }
 _DERIVED = {S_BASE + 8 * s + q: _DERIVED_LAYOUT["summary", q] for s in range(3) for q in range(4)}
 _DERIVED.update({E_BASE + 8 * s + q: _DERIVED_LAYOUT["errors", q] for s in range(2) for q in range(6)})
 _DERIVED.update({L_BASE + q: _DERIVED_LAYOUT["data", q] for q in range(2)})
+_DERIVED.update({EV_BASE + 8 * s + q: _DERIVED_LAYOUT["event", q] for s in range(2) for q in range(7)})
 
 
 def _fetch(lib, h, f: int, dtype=None) -> np.ndarray:
@@ -165,6 +198,49 @@ def _observation_arrays(t, d, N, times, data, noise_var, components):
     if not np.all(np.isfinite(noise)) or np.any(noise <= 0):
         raise OdefError("data_loglik: noise variances must be finite and positive")
     return saves.astype(np.int64), comps.astype(np.int64), values, np.ascontiguousarray(noise), per_traj
+
+
+@dataclass
+class Events:
+    """Located level crossings per trajectory (`EnsembleSolution.events`), trajectory-major.  `count [N]` is the number of
+    crossings of the whole trajectory and may exceed the K = `max_events` slots; slot s < min(count, K) of trajectory i holds the
+    time `t[i, s]`, its standard deviation `t_std[i, s]` (sqrt of Var u_c(t*) / E[u'_c(t*)]^2), the solution `u[i, s, :]` there, the
+    `direction` (+1 up, -1 down), the left save `save` of the step that holds it and the dense evaluations spent, `neval`.
+    Unused slots: NaN, direction 0, save -1, neval 0."""
+    count: np.ndarray
+    t: np.ndarray
+    t_std: np.ndarray
+    u: np.ndarray
+    direction: np.ndarray
+    save: np.ndarray
+    neval: np.ndarray
+
+    @classmethod
+    def from_abi(cls, a):
+        """From the seven ABI arrays (count [N], time / var [K, N], u [K, d, N], direction / save / neval [K, N])."""
+        count, time, var, u, direction, save, neval = a
+        with np.errstate(invalid="ignore"):
+            std = np.sqrt(var.T)
+        return cls(count, np.ascontiguousarray(time.T), np.ascontiguousarray(std), np.ascontiguousarray(u.transpose(2, 0, 1)),
+                   np.ascontiguousarray(direction.T), np.ascontiguousarray(save.T), np.ascontiguousarray(neval.T))
+
+    @classmethod
+    def concatenate(cls, parts):
+        return cls(*(np.concatenate([getattr(p, k) for p in parts]) for k in ("count", "t", "t_std", "u", "direction", "save", "neval")))
+
+
+def _event_arrays(d, N, component, level, direction, max_events):
+    """The two inputs of the event location in the ABI layout, validated on the host: (spec int64 [3], level [1] or [N])."""
+    if int(component) != component or not 0 <= int(component) < d:
+        raise OdefError(f"events: component must be an integer within 0 .. {d - 1}")
+    if direction not in (-1, 0, 1):
+        raise OdefError("events: direction must be -1 (down), 0 (both) or +1 (up)")
+    if int(max_events) != max_events or int(max_events) < 1:
+        raise OdefError("events: max_events must be a positive integer")
+    lvl = np.atleast_1d(np.asarray(level, np.float64))
+    if lvl.shape not in ((1,), (N,)):
+        raise OdefError(f"events: level must be a scalar or have shape ({N},), got {lvl.shape}")
+    return np.array([int(component), int(direction), int(max_events)], np.int64), np.ascontiguousarray(lvl)
 
 
 def _to_device(arrays, device):
@@ -410,6 +486,20 @@ class DeviceGroup:
             parts.append(Context._data_loglik(self.lib, self.lib.odef_group_ctx(self._h, g), bufs))
         return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
 
+    def events(self, component, level=0.0, direction=0, max_events=1, smoothed=False) -> "Events":
+        """Level crossings of the WHOLE ensemble (`EnsembleSolution.events`): the same spec goes to every shard through
+        `odef_group_ctx`, a per-trajectory level is split by `odef_group_shard`, every shard runs the pass on its own device and
+        the results are joined along the trajectory axis."""
+        spec, lvl = _event_arrays(self.d, self.N, component, level, direction, max_events)
+        self._event_bufs = []
+        parts = []
+        for g in range(self.G):
+            first, count = self.shard(g)
+            bufs = _to_device((spec, lvl if lvl.size == 1 else lvl[first:first + count]), self._devices[g])
+            self._event_bufs.append(bufs)
+            parts.append(Context._events(self.lib, self.lib.odef_group_ctx(self._h, g), self, int(bool(smoothed)), bufs))
+        return Events.concatenate(parts)
+
     def ensemble_moments(self, source: int):
         """Ensemble summary of the WHOLE ensemble: every shard reduces its own records on its device (`odef_summary_field`),
         the per-shard blocks (kilobytes) are pooled on the host with `merge_moments`.  Returns (count, mean, within, between)."""
@@ -644,6 +734,34 @@ class Context:
         (loglik [N], mahalanobis [N]).  The first request after the records or the observations changed launches the pass."""
         return self._data_loglik(self.lib, self._h)
 
+    def bind_event(self, spec_ptr: int, level_ptr: int, per_trajectory: bool):
+        """The inputs of `events`, device memory that stays the caller's (read only): spec int64 [3] {component, direction, K}
+        and the level, one double or -- `per_trajectory` -- [N]."""
+        for f, ptr, nb in ((EV_SPEC, spec_ptr, 24), (EV_LEVEL, level_ptr, 8 * (self.N if per_trajectory else 1))):
+            self._chk(self.lib.odef_bind_device(self._h, f, _vp(ptr) if ptr else None, nb))
+
+    @staticmethod
+    def _events(lib, h, shape, source: int, bufs=None) -> "Events":
+        """`Events` of the context `h` (`shape`: anything with d and N of that context's family; the arrays are reshaped by their
+        own trajectory count); `bufs`: torch tensors (spec, level) to bind first."""
+        if bufs is not None:
+            for f, b in zip((EV_SPEC, EV_LEVEL), bufs):
+                if lib.odef_bind_device(h, f, _vp(b.data_ptr()), b.numel() * 8) != 0:
+                    raise OdefError(lib.odef_last_error(h).decode())
+        count = _fetch(lib, h, event_field(source, EV_COUNT))
+        n, d = count.size, shape.d
+        arr = [count]
+        for qty in range(1, 7):
+            a = _fetch(lib, h, event_field(source, qty))
+            arr.append(a.reshape(-1, d, n) if qty == EV_U else a.reshape(-1, n))
+        return Events.from_abi(arr)
+
+    def events(self, source: int) -> "Events":
+        """Level crossings per trajectory for the bound spec and level (`bind_event`) on the filter (0) or smoothed (1) posterior,
+        located on the device (`odef_event_field`).  The first request after the records or an input changed launches the pass
+        (a scan of one row of the mean records, then bracketed Newton on the dense posterior); later ones read the cache."""
+        return self._events(self.lib, self._h, self, source)
+
     def device_ptr(self, f: int):
         p, b = _vp(), C.c_size_t()
         self._chk(self.lib.odef_get_device(self._h, f, C.byref(p), C.byref(b)))
@@ -654,7 +772,7 @@ class Context:
 
     def kernel_name(self, which=0) -> str:
         """Name of the kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) / data-likelihood
-        (4) pass launched, as a profiler prints it."""
+        (4) / event-location (5) pass launched, as a profiler prints it."""
         buf = C.create_string_buffer(256)
         self._chk(self.lib.odef_kernel_name(self._h, which, buf, 256))
         return buf.value.decode()
@@ -1105,6 +1223,21 @@ class EnsembleSolution:
         arrays = _observation_arrays(self.t, self.d, self.ctx.N, times, data, noise_var, components)
         self._obs_bufs = _to_device(arrays[:4], self.ctx.cfg.device)  # device memory owned by torch, kept alive by the solution
         return Context._data_loglik(self.ctx.lib, self.ctx._h, self._obs_bufs)
+
+    def events(self, component, level=0.0, direction=0, max_events=1, smoothed: Optional[bool] = None) -> Events:
+        """When does each trajectory cross a level?  The times at which component `component` of the posterior mean crosses
+        `level` (a scalar, or [N] per trajectory) -- the answer of a `ContinuousCallback` with condition u[c] - level, asked of the
+        finished posterior, on the device.  direction +1 keeps upward crossings, -1 downward, 0 both; the first `max_events` per
+        trajectory are located, `count` counts all.  Works on fixed and adaptive grids (`save` is then a raw record index,
+        `raw_index`).  smoothed=None: the smoothed posterior if the solution is smoothed.  The state carries u', so the root is
+        found by Newton on the dense posterior mean without extra evaluations of the field, and the posterior variance at the
+        root gives `t_std`.  A crossing that does not show at the two ends of a step (a double root inside one step) is not
+        detected.  On the filter posterior (smoothed=False) the interpolant jumps at every save by the measurement update; a
+        crossing that happens inside such a jump is reported at the save itself, with the stored state.  Returns `Events`."""
+        sm = self.smoothed if smoothed is None else bool(smoothed)
+        arrays = _event_arrays(self.d, self.ctx.N, component, level, direction, max_events)
+        self._event_bufs = _to_device(arrays, self.ctx.cfg.device)  # device memory owned by torch, kept alive by the solution
+        return Context._events(self.ctx.lib, self.ctx._h, self.ctx, int(sm), self._event_bufs)
 
     def summary(self, t=None, smoothed: Optional[bool] = None) -> EnsembleSummary:
         """Mean path of the ensemble and its uncertainty, reduced on the device (`odef_summary_field`): nothing but the four
