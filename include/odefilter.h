@@ -153,7 +153,7 @@ typedef enum {
  *   the dense records     DENSE_MEAN, DENSE_COV_TRIL                   source 2
  *   the problem           u0, p, t0
  *   the bound truth       ODEF_E_REFERENCE
- *   the observations      ODEF_L_OBS_SAVE / COMPONENT / VALUE / NOISE
+ *   the observations      ODEF_L_OBS_SAVE / COMPONENT / VALUE / NOISE / TIME
  *   the event spec        ODEF_EV_SPEC / ODEF_EV_LEVEL
  * and what is derived from what:
  *   the summary of source k       its record set; a new problem drops it as well
@@ -267,7 +267,21 @@ typedef enum {
  * that is not finite and positive; a context that kept only the final state.  A non-positive pivot of S or a NaN in a record the
  * sweep reads gives NaN for that trajectory only; a trajectory whose RETCODE is not Success still gets a number.
  * odef_kernel_time_ms / odef_kernel_name report the last pass as which = 4; its n_launches counts the passes launched since the
- * context was created (a request served from the cache leaves it unchanged). */
+ * context was created (a request served from the cache leaves it unchanged).
+ *
+ * Observations at ARBITRARY TIMES, after fixed-grid and after adaptive solves: bind
+ *   ODEF_L_OBS_TIME       double [M]           times tau_1 < ... < tau_M, t0 <= tau_1 (fixed grid: tau_M <= the last save time)
+ * INSTEAD of ODEF_L_OBS_SAVE (COMPONENT, VALUE, NOISE as above).  The sweep then runs per trajectory over its own records
+ * t_0 .. t_{n-1} (n = n_save on a fixed grid, NSAVED[i] with the times T after an adaptive solve) plus one node per tau_j that is
+ * none of its save times: for t_k < tau_j < t_{k+1} the filter's prediction from record k over h1 = tau_j - t_k, in the
+ * coordinates of P(h1), with sigma2 = DIFFUSION[k + 1] -- what odef_dense_output forms for the filter source; two nodes of one
+ * step are both predicted from record k.  A node takes the RTS step above against xi with h2 = (time of xi) - tau_j in the
+ * coordinates of P(h2) and the same DIFFUSION[k + 1], and is then observed; tau_j == t_k is observed at save k.  A tau_j above a
+ * trajectory's own last save (an adaptive solve whose RETCODE is not Success) gives NaN for that trajectory only.  Which pass runs:
+ * OBS_TIME bound and OBS_SAVE not, this one (odef::data_loglik_times_kernel, named by which = 4); OBS_SAVE bound and OBS_TIME
+ * not, the one above, unchanged; both bound, refused.  Refused in addition: a (d, q) outside d <= 4, q <= 5, d (q + 1) <= 12
+ * (the pairs odef_dense_output serves per lane) and the workgroup-per-trajectory path; times that are not finite, not strictly
+ * increasing, below t0 or, on a fixed grid, above the last save.  TIME, COMPONENT and NOISE are validated on the host. */
 typedef enum {
   ODEF_L_BASE = 192,
   ODEF_L_DATA_LOGLIK = 192,
@@ -275,7 +289,8 @@ typedef enum {
   ODEF_L_OBS_SAVE = 200,      /* odef_bind_device only */
   ODEF_L_OBS_COMPONENT = 201, /* odef_bind_device only */
   ODEF_L_OBS_VALUE = 202,     /* odef_bind_device only */
-  ODEF_L_OBS_NOISE = 203      /* odef_bind_device only */
+  ODEF_L_OBS_NOISE = 203,     /* odef_bind_device only */
+  ODEF_L_OBS_TIME = 204       /* odef_bind_device only */
 } odef_data_field;
 
 /* Event location per trajectory, on the device: the times at which component c of the posterior mean crosses a level -- what a

@@ -72,6 +72,7 @@ const L_OBS_SAVE = 200
 const L_OBS_COMPONENT = 201
 const L_OBS_VALUE = 202
 const L_OBS_NOISE = 203
+const L_OBS_TIME = 204
 # event location per trajectory (odef_event_field, include/odefilter.h): id = EV_BASE + 8 * source + quantity, two inputs that
 # odef_bind_device alone takes.  UNTESTED like the rest of this file.
 const EV_BASE = 256
@@ -167,7 +168,23 @@ the caller's: `saves` Int64 [M] (0-based save indices, increasing), `comps` Int6
 `values` Float64 [M][o] or [M][o][N], `noise` Float64 [o] variances, each given as `(ptr, bytes)`.  UNTESTED.
 """
 function data_loglik(ctx, n_traj::Integer, saves, comps, values, noise)
-    for (f, (ptr, bytes)) in ((L_OBS_SAVE, saves), (L_OBS_COMPONENT, comps), (L_OBS_VALUE, values), (L_OBS_NOISE, noise))
+    for (f, (ptr, bytes)) in ((L_OBS_TIME, (C_NULL, 0)), (L_OBS_SAVE, saves), (L_OBS_COMPONENT, comps), (L_OBS_VALUE, values), (L_OBS_NOISE, noise))
+        check(ccall((:odef_bind_device, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Csize_t), ctx, f, ptr, bytes), ctx)
+    end
+    return fetch(ctx, L_DATA_LOGLIK, Float64, n_traj), fetch(ctx, L_DATA_MAHALANOBIS, Float64, n_traj)
+end
+
+"""
+    data_loglik_times(ctx, n_traj, times, comps, values, noise) -> (loglik, mahalanobis)
+
+The same likelihood with the observations given by TIME, after a fixed-grid or an adaptive solve: `times` is a DEVICE pointer
+`(ptr, bytes)` to Float64 [M], strictly increasing from t0 on; the times need not be save times (a node predicted by the filter is
+inserted per trajectory).  The other arguments as for `data_loglik`.  A trajectory whose records end before the last time gets
+NaN.  UNTESTED.
+"""
+function data_loglik_times(ctx, n_traj::Integer, times, comps, values, noise)
+    for (f, (ptr, bytes)) in ((L_OBS_SAVE, (C_NULL, 0)), (L_OBS_TIME, times), (L_OBS_COMPONENT, comps), (L_OBS_VALUE, values),
+                              (L_OBS_NOISE, noise))
         check(ccall((:odef_bind_device, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Csize_t), ctx, f, ptr, bytes), ctx)
     end
     return fetch(ctx, L_DATA_LOGLIK, Float64, n_traj), fetch(ctx, L_DATA_MAHALANOBIS, Float64, n_traj)

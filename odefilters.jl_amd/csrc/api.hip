@@ -87,7 +87,7 @@ struct odef_ctx {
   const double* err_ref = nullptr;  // ODEF_E_REFERENCE: the bound truth [n_save][d][N] (caller memory, read only)
   size_t err_ref_bytes = 0;
   DataLikState datalik;  // cached data log-likelihood of the filter records (odef_data_field)
-  Buf obs[4];            // ODEF_L_OBS_SAVE / COMPONENT / VALUE / NOISE: caller memory, read only
+  Buf obs[5];            // ODEF_L_OBS_SAVE / COMPONENT / VALUE / NOISE / TIME: caller memory, read only
   EventsState events;    // cached event times of the filter and smoothed posterior (odef_event_field)
   Buf evin[2];           // ODEF_EV_SPEC / ODEF_EV_LEVEL: caller memory, read only
   // odef_group runs its shards concurrently: with `defer` set, odef_solve_* / odef_smooth return after the launch and
@@ -442,24 +442,33 @@ int errors_fetch(odef_ctx* c, int field, const char* who, void** ptr) {
   return 0;
 }
 
-// odef_data_field: the two outputs, and the four inputs that odef_bind_device alone takes
+// odef_data_field: the two outputs, and the five inputs that odef_bind_device alone takes
 bool is_datalik_output(int field) { return field == ODEF_L_DATA_LOGLIK || field == ODEF_L_DATA_MAHALANOBIS; }
-bool is_datalik_input(int field) { return field >= ODEF_L_OBS_SAVE && field <= ODEF_L_OBS_NOISE; }
+bool is_datalik_input(int field) { return field >= ODEF_L_OBS_SAVE && field <= ODEF_L_OBS_TIME; }
+// the observations are given by time (ODEF_L_OBS_TIME bound: the pass of datalik_times.hip), not by save index
+bool datalik_by_time(const odef_ctx* c) { return c->obs[4].ptr != nullptr; }
 
 int datalik_check(const odef_ctx* c, int, const char* who) {
+  if (c->obs[0].ptr && c->obs[4].ptr)
+    return fail(c, "%s: data log-likelihood: ODEF_L_OBS_SAVE and ODEF_L_OBS_TIME are both bound; the observations are given by save "
+                   "index or by time: unbind one of the two (odef_bind_device with NULL)", who);
   if (!c->solved) return fail(c, "%s: data log-likelihood requested before a solve (call odef_solve_* first)", who);
-  if (c->adaptive)
+  const bool by_time = datalik_by_time(c);
+  if (c->adaptive && !by_time)
     return fail(c, "%s: data log-likelihood after an adaptive solve: the observation times are per ensemble, the grid of an adaptive "
                    "solve is per trajectory; solve on a fixed grid that contains the observation times", who);
   if (is_mv(c->cfg.diffusion))
     return fail(c, "%s: data log-likelihood is built for the scalar diffusion models, not :dynamicMV / :fixedMV", who);
+  if (by_time && (team_path(c) || !datalik_times_has(c->d, c->q)))
+    return fail(c, "%s: data log-likelihood at observation times has no kernel for (d, q) = (%d, %d); built for d <= 4, q <= 5, "
+                   "d (q + 1) <= 12", who, c->d, c->q);
   if (team_path(c) || !datalik_has(c->d, c->q))
     return fail(c, "%s: data log-likelihood has no kernel for (d, q) = (%d, %d); built for d <= 4, q <= 5, d (q + 1) <= 20", who, c->d, c->q);
   if (c->cfg.save_mode != ODEF_SAVE_EVERYSTEP || c->n_save < 2)
     return fail(c, "%s: data log-likelihood needs the records of every step, this context kept only the final state "
                    "(ODEF_SAVE_EVERYSTEP)", who);
   static const char* const kName[4] = {"ODEF_L_OBS_SAVE", "ODEF_L_OBS_COMPONENT", "ODEF_L_OBS_VALUE", "ODEF_L_OBS_NOISE"};
-  for (int k = 0; k < 4; ++k)
+  for (int k = by_time ? 1 : 0; k < 4; ++k)
     if (!c->obs[k].ptr) return fail(c, "%s: data log-likelihood input missing: bind %s with odef_bind_device", who, kName[k]);
   return 0;
 }
@@ -467,8 +476,45 @@ int datalik_check(const odef_ctx* c, int, const char* who) {
 // the cached array of a data log-likelihood field; the first request after the records or an input changed runs the pass
 size_t datalik_bytes(const odef_ctx* c, int) { return (size_t)c->cfg.n_traj * sizeof(double); }
 
+// the pass over every trajectory's own records with a node per observation time (ODEF_L_OBS_TIME)
+int datalik_times_ensure(odef_ctx* c, const char* who) {
+  DataLikTimesRequest r;
+  std::memset(&r, 0, sizeof r);
+  r.pc = &c->pc;
+  r.N = c->cfg.n_traj;
+  r.n_save = c->n_save;
+  r.d = c->d;
+  r.q = c->q;
+  r.adaptive = c->adaptive;
+  r.t0 = c->adaptive || c->tgrid.empty() ? c->t0 : c->tgrid.front();
+  r.t_last = c->tgrid.empty() ? 0.0 : c->tgrid.back();
+  r.tgrid = c->d_tgrid;
+  r.tsave = (const double*)c->f[ODEF_F_T].ptr;
+  r.nsaved = (const int*)c->f[ODEF_F_NSAVED].ptr;
+  r.mean = (const double*)c->f[ODEF_F_MEAN].ptr;
+  r.cov = (const double*)c->f[ODEF_F_COV_TRIL].ptr;
+  r.diff = (const double*)c->f[ODEF_F_DIFFUSION].ptr;
+  if (!r.mean || !r.cov || !r.diff || (c->adaptive ? !r.tsave || !r.nsaved : !r.tgrid || (long)c->tgrid.size() != c->n_save))
+    return fail(c, "%s: the filter records hold no data", who);
+  r.obs_time = (const double*)c->obs[4].ptr;
+  r.obs_comp = c->obs[1].ptr;
+  r.obs_val = (const double*)c->obs[2].ptr;
+  r.obs_noise = (const double*)c->obs[3].ptr;
+  r.time_bytes = c->obs[4].bytes;
+  r.comp_bytes = c->obs[1].bytes;
+  r.val_bytes = c->obs[2].bytes;
+  r.noise_bytes = c->obs[3].bytes;
+  std::string err;
+  if (datalik_times_run(c->datalik, r, c->stream, &c->ms[kPassDataLik], &c->nl[kPassDataLik], c->kname[kPassDataLik],
+                        sizeof c->kname[kPassDataLik], err))
+    return fail(c, "%s: %s", who, err.c_str());
+  return 0;
+}
+
 int datalik_fetch(odef_ctx* c, int field, const char* who, void** ptr) {
-  if (!c->datalik.valid) {
+  if (!c->datalik.valid && datalik_by_time(c)) {
+    if (datalik_times_ensure(c, who)) return -1;
+  } else if (!c->datalik.valid) {
     DataLikRequest r;
     std::memset(&r, 0, sizeof r);
     r.pc = &c->pc;

@@ -46,4 +46,33 @@ int datalik_run(DataLikState& st, const DataLikRequest& r, hipStream_t stream, f
                 std::string& err);
 void datalik_free(DataLikState& st);
 
+// The same likelihood at arbitrary observation times, on fixed and on adaptive grids (datalik_times.hip): the sweep
+// runs over every trajectory's own records plus one predicted node per time that is no save.  Same state, same outputs.
+struct DataLikTimesRequest {
+  const PriorConsts* pc;
+  long N, n_save;          // fixed grid: number of saves; adaptive: capacity of the records
+  int d, q;
+  int adaptive;
+  double t0;               // the first save time (of every trajectory)
+  double t_last;           // fixed grid: the last save time
+  const double* tgrid;     // fixed: [n_save], device
+  const double* tsave;     // adaptive: [n_save][N]
+  const int* nsaved;       // adaptive: [N]
+  const double* mean;      // filter records, ABI layout
+  const double* cov;
+  const double* diff;
+  const double* obs_time;  // [M] doubles
+  const void* obs_comp;    // [o] int64
+  const double* obs_val;   // [M][o] or [M][o][N]
+  const double* obs_noise; // [o]
+  size_t time_bytes, comp_bytes, val_bytes, noise_bytes;
+};
+
+// true when data_loglik_times_kernel<d, q> is instantiated (d <= 4, q <= 5, d (q + 1) <= 12)
+bool datalik_times_has(int d, int q);
+// Copies times, components and noise to the host (M + 2 o words) and validates them, runs the pass on `stream` (one launch) into
+// `st` and waits.  Returns 0, or -1 with `err` set.
+int datalik_times_run(DataLikState& st, const DataLikTimesRequest& r, hipStream_t stream, float* ms, int* n_launches, char* kname,
+                      size_t kname_n, std::string& err);
+
 }  // namespace odef

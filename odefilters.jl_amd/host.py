@@ -97,6 +97,8 @@ DATA_FIELDS = {
     "ODEF_L_DATA_LOGLIK": 192, "ODEF_L_DATA_MAHALANOBIS": 193,
     "ODEF_L_OBS_SAVE": 200, "ODEF_L_OBS_COMPONENT": 201, "ODEF_L_OBS_VALUE": 202, "ODEF_L_OBS_NOISE": 203,
 }
+L_OBS_TIME = 204  # odef_bind_device only: observation times instead of save indices (fixed and adaptive grids)
+DATA_TIME_FIELDS = {"ODEF_L_OBS_TIME": 204}
 K_DATA_LOGLIK = 4  # `which` of odef_kernel_time_ms / odef_kernel_name
 
 # event location per trajectory (odef_event_field, include/odefilter.h): id = EV_BASE + 8 * source + quantity
@@ -177,12 +179,46 @@ def _observation_arrays(t, d, N, times, data, noise_var, components):
         raise OdefError(f"data_loglik: observation times must equal save times of the solution exactly; not on the grid: {bad[:4]}")
     if np.any(np.diff(saves) <= 0):
         raise OdefError("data_loglik: observation times must be strictly increasing")
+    return (saves.astype(np.int64),) + _observation_values(d, N, saves.size, data, noise_var, components)
+
+
+def _observation_time_arrays(d, N, times, data, noise_var, components, t0=None, t_last=None):
+    """The inputs of the data log-likelihood at arbitrary times in the ABI layout, validated on the host: (times float64 [M],
+    comps int64 [o], values [M, o] or [M, o, N], noise [o], per_trajectory).  `t0`: the first save time; `t_last`: the last save
+    time of a fixed grid (an adaptive solve ends per trajectory: a time above a trajectory's own last save gives NaN there)."""
+    times = np.atleast_1d(np.asarray(times, np.float64))
+    if times.ndim != 1 or times.size == 0:
+        raise OdefError("data_loglik: times must be a non-empty 1-d array")
+    if not np.all(np.isfinite(times)):
+        raise OdefError("data_loglik: observation times must be finite")
+    if np.any(np.diff(times) <= 0):
+        raise OdefError("data_loglik: observation times must be strictly increasing")
+    if t0 is not None and times[0] < t0:
+        raise OdefError(f"data_loglik: observation time {times[0]!r} lies before the first save t0 = {t0!r}")
+    if t_last is not None and times[-1] > t_last:
+        raise OdefError(f"data_loglik: observation time {times[-1]!r} lies above the last save of the grid, {t_last!r} (a time meant "
+                        "as that save must equal it exactly)")
+    return (np.ascontiguousarray(times),) + _observation_values(d, N, times.size, data, noise_var, components)
+
+
+def _on_grid(t, times) -> bool:
+    """True when every entry of `times` equals an entry of the fixed save grid `t` exactly."""
+    t = np.asarray(t, np.float64).reshape(-1)
+    times = np.atleast_1d(np.asarray(times, np.float64))
+    if times.ndim != 1 or times.size == 0 or t.size == 0:
+        return True  # (left to the validation of the save path)
+    k = np.minimum(np.searchsorted(t, times), t.size - 1)
+    return bool(np.all(t[k] == times))
+
+
+def _observation_values(d, N, M, data, noise_var, components):
+    """(comps int64 [o], values [M, o] or [M, o, N], noise [o], per_trajectory) of M observations, validated."""
     comps = np.arange(d) if components is None else np.atleast_1d(np.asarray(components))
     if comps.ndim != 1 or comps.size == 0 or not np.issubdtype(comps.dtype, np.integer):
         raise OdefError("data_loglik: components must be a non-empty 1-d integer array")
     if np.any(comps < 0) or np.any(comps >= d) or np.any(np.diff(comps) <= 0):
         raise OdefError(f"data_loglik: components must be strictly increasing within 0 .. {d - 1}")
-    M, o = saves.size, comps.size
+    o = comps.size
     data = np.asarray(data, np.float64)
     if data.shape == (M, o):
         per_traj, values = False, np.ascontiguousarray(data)
@@ -197,7 +233,7 @@ def _observation_arrays(t, d, N, times, data, noise_var, components):
         raise OdefError(f"data_loglik: noise_var must be a scalar or have shape ({o},), got {noise.shape}")
     if not np.all(np.isfinite(noise)) or np.any(noise <= 0):
         raise OdefError("data_loglik: noise variances must be finite and positive")
-    return saves.astype(np.int64), comps.astype(np.int64), values, np.ascontiguousarray(noise), per_traj
+    return comps.astype(np.int64), values, np.ascontiguousarray(noise), per_traj
 
 
 @dataclass
@@ -370,6 +406,7 @@ class DeviceGroup:
         cfg.save_mode = SAVE_EVERYSTEP if (save_everystep or smooth) else SAVE_FINAL
         cfg.device, cfg.want_loglik, cfg.n_traj = -1, int(want_loglik), n_traj
         self.d, self.D, self.N, self.G = d, d * (order + 1), n_traj, n_devices
+        self._adaptive = False  # the last solve was adaptive (its T is [n_save][N], its grid per trajectory)
         self.TRI, self.mv = self.D * (self.D + 1) // 2, diffusion in MV_DIFFUSIONS
         ids = (C.c_int32 * n_devices)(*device_ids) if device_ids is not None else None
         h = _vp()
@@ -412,9 +449,11 @@ class DeviceGroup:
     def solve_fixed(self, tgrid):
         tg = np.ascontiguousarray(tgrid, dtype=np.float64)
         self._chk(self.lib.odef_group_solve_fixed(self._h, _as_dp(tg), len(tg)))
+        self._adaptive = False
 
     def solve_adaptive(self, t1, abstol=1e-6, reltol=1e-3, dt0=1e-3, max_steps=4096):
         self._chk(self.lib.odef_group_solve_adaptive(self._h, float(t1), float(abstol), float(reltol), float(dt0), None, int(max_steps)))
+        self._adaptive = True
 
     def smooth(self):
         self._chk(self.lib.odef_group_smooth(self._h))
@@ -470,20 +509,27 @@ class DeviceGroup:
     def data_loglik(self, times, data, noise_var, components=None):
         """Data log-likelihood of the WHOLE ensemble (`EnsembleSolution.data_loglik`): the same observations go to every shard
         through `odef_group_ctx`, per-trajectory values are split by `odef_group_shard`, every shard runs the pass on its own
-        device and the results are joined along the trajectory axis.  Returns (loglik [N], mahalanobis [N])."""
+        device and the results are joined along the trajectory axis.  Times that all equal saves of a fixed grid go by save
+        index, any others and every adaptive solve by time (`bind_observation_times`).  Returns (loglik [N], mahalanobis [N])."""
+        adaptive = self._adaptive
         try:
             t = _fetch(self.lib, self.lib.odef_group_ctx(self._h, 0), F_T)
         except OdefError:
-            raise OdefError("data_loglik: needs a fixed-grid solve first") from None
-        saves, comps, values, noise, per_traj = _observation_arrays(t, self.d, self.N, times, data, noise_var, components)
+            raise OdefError("data_loglik: needs a solve first") from None
+        by_time = adaptive or not _on_grid(t, times)
+        if by_time:
+            first, comps, values, noise, per_traj = _observation_time_arrays(self.d, self.N, times, data, noise_var, components,
+                                                                             None if adaptive else t[0], None if adaptive else t[-1])
+        else:
+            first, comps, values, noise, per_traj = _observation_arrays(t, self.d, self.N, times, data, noise_var, components)
         self._obs_bufs = []
         parts = []
         for g in range(self.G):
-            first, count = self.shard(g)
-            vals = values[:, :, first:first + count] if per_traj else values
-            bufs = _to_device((saves, comps, vals, noise), self._devices[g])
+            lo, count = self.shard(g)
+            vals = values[:, :, lo:lo + count] if per_traj else values
+            bufs = _to_device((first, comps, vals, noise), self._devices[g])
             self._obs_bufs.append(bufs)
-            parts.append(Context._data_loglik(self.lib, self.lib.odef_group_ctx(self._h, g), bufs))
+            parts.append(Context._data_loglik(self.lib, self.lib.odef_group_ctx(self._h, g), bufs, by_time))
         return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
 
     def events(self, component, level=0.0, direction=0, max_events=1, smoothed=False) -> "Events":
@@ -715,21 +761,36 @@ class Context:
         """The observations of `data_loglik`, device memory that stays the caller's (read only): save indices int64 [M],
         components int64 [o], values double [M][o] (shared) or [M][o][N] (per trajectory), noise variances double [o]."""
         nv = M * o * (self.N if per_trajectory else 1) * 8
-        for f, ptr, nb in ((L_OBS_SAVE, save_ptr, M * 8), (L_OBS_COMPONENT, comp_ptr, o * 8), (L_OBS_VALUE, value_ptr, nv),
-                           (L_OBS_NOISE, noise_ptr, o * 8)):
+        for f, ptr, nb in ((L_OBS_TIME, 0, 0), (L_OBS_SAVE, save_ptr, M * 8), (L_OBS_COMPONENT, comp_ptr, o * 8),
+                           (L_OBS_VALUE, value_ptr, nv), (L_OBS_NOISE, noise_ptr, o * 8)):
+            self._chk(self.lib.odef_bind_device(self._h, f, _vp(ptr) if ptr else None, nb))
+
+    def bind_observation_times(self, time_ptr: int, comp_ptr: int, value_ptr: int, noise_ptr: int, M: int, o: int,
+                               per_trajectory: bool):
+        """The observations of `data_loglik` given by TIME, after a fixed-grid or an adaptive solve: times double [M], strictly
+        increasing from t0 on (they need not be save times); the other three as in `bind_observations`.  Unbinds the save
+        indices: the two ways of saying where the observations lie exclude each other."""
+        nv = M * o * (self.N if per_trajectory else 1) * 8
+        for f, ptr, nb in ((L_OBS_SAVE, 0, 0), (L_OBS_TIME, time_ptr, M * 8), (L_OBS_COMPONENT, comp_ptr, o * 8),
+                           (L_OBS_VALUE, value_ptr, nv), (L_OBS_NOISE, noise_ptr, o * 8)):
             self._chk(self.lib.odef_bind_device(self._h, f, _vp(ptr) if ptr else None, nb))
 
     @staticmethod
-    def _data_loglik(lib, h, bufs=None):
-        """(loglik [N], mahalanobis [N]) of the context `h`; `bufs`: torch tensors (saves, comps, values, noise) to bind first."""
+    def _data_loglik(lib, h, bufs=None, by_time=False):
+        """(loglik [N], mahalanobis [N]) of the context `h`; `bufs`: torch tensors (saves or -- `by_time` -- times, comps, values,
+        noise) to bind first; the other of OBS_SAVE / OBS_TIME is unbound."""
         if bufs is not None:
-            for f, b in zip((L_OBS_SAVE, L_OBS_COMPONENT, L_OBS_VALUE, L_OBS_NOISE), bufs):
+            first, other = (L_OBS_TIME, L_OBS_SAVE) if by_time else (L_OBS_SAVE, L_OBS_TIME)
+            if lib.odef_bind_device(h, other, None, 0) != 0:
+                raise OdefError(lib.odef_last_error(h).decode())
+            for f, b in zip((first, L_OBS_COMPONENT, L_OBS_VALUE, L_OBS_NOISE), bufs):
                 if lib.odef_bind_device(h, f, _vp(b.data_ptr()), b.numel() * 8) != 0:
                     raise OdefError(lib.odef_last_error(h).decode())
         return tuple(_fetch(lib, h, f) for f in (L_DATA_LOGLIK, L_DATA_MAHALANOBIS))
 
     def data_loglik(self):
-        """Per-trajectory log-likelihood of the bound observations under the posterior of the last fixed-grid solve, and the
+        """Per-trajectory log-likelihood of the bound observations under the posterior of the last solve (by save index: fixed
+        grids; by time, `bind_observation_times`: fixed and adaptive), and the
         Mahalanobis sum (chi^2 with M o degrees of freedom for a calibrated model), reduced on the device (`odef_data_field`):
         (loglik [N], mahalanobis [N]).  The first request after the records or the observations changed launches the pass."""
         return self._data_loglik(self.lib, self._h)
@@ -1213,16 +1274,21 @@ class EnsembleSolution:
         """Log-likelihood of noisy observations of the solution per trajectory, on the device: for y_j = u(times[j])[components] +
         N(0, diag noise_var), the marginal likelihood under the Gauss-Markov posterior the filter records and the smoother's
         backward transitions define (Tronarp, Bosch, Hennig 2022; later versions of the reference: `fenrir_data_loglik`).
-        `times` must equal entries of `sol.t` exactly; `data` is [M, o] (shared) or [N, M, o]; `noise_var` a scalar or [o];
+        `times` are strictly increasing, from t0 on; `data` is [M, o] (shared) or [N, M, o]; `noise_var` a scalar or [o];
         `components` defaults to all d.  Returns (loglik [N], mahalanobis [N]): with per-trajectory u0 or p, argmax of the first
         is the candidate that explains the data best; the second is chi^2 with M o degrees of freedom for a calibrated model.
-        Fixed grids only."""
-        if self.adaptive:
-            raise OdefError("data_loglik: observation times are per ensemble, the grid of an adaptive solve is per trajectory; "
-                            "solve on a fixed grid that contains the observation times")
-        arrays = _observation_arrays(self.t, self.d, self.ctx.N, times, data, noise_var, components)
+        After a fixed-grid solve whose `times` all equal entries of `sol.t` the sweep runs over the saves; otherwise -- times off
+        the grid (up to its last save), or an adaptive solve -- over every trajectory's own records with the filter's prediction
+        inserted at each time that is no save.  A trajectory of an adaptive solve whose records end before the last time gets NaN."""
+        by_time = self.adaptive or not _on_grid(self.t, times)
+        if by_time:
+            t = None if self.adaptive else self.t
+            arrays = _observation_time_arrays(self.d, self.ctx.N, times, data, noise_var, components,
+                                              None if t is None else t[0], None if t is None else t[-1])
+        else:
+            arrays = _observation_arrays(self.t, self.d, self.ctx.N, times, data, noise_var, components)
         self._obs_bufs = _to_device(arrays[:4], self.ctx.cfg.device)  # device memory owned by torch, kept alive by the solution
-        return Context._data_loglik(self.ctx.lib, self.ctx._h, self._obs_bufs)
+        return Context._data_loglik(self.ctx.lib, self.ctx._h, self._obs_bufs, by_time)
 
     def events(self, component, level=0.0, direction=0, max_events=1, smoothed: Optional[bool] = None) -> Events:
         """When does each trajectory cross a level?  The times at which component `component` of the posterior mean crosses
