@@ -216,3 +216,75 @@ def emul_solve(rhs_id, d, q, ek1, u0s, p, *, team=False, tgrid=None, adaptive=Fa
         assert rc == 0, rc
         out["dense_samples"] = smp.transpose(3, 0, 1, 2)  # [N, n_q, D, n_samples]
     return out
+
+
+_LIB_MV = None
+
+
+def lib_mv():
+    """tests/emul/libodef_emul_mv.so: emul.cpp plus the MV instantiations of the lane filter and the row-team smoother."""
+    global _LIB_MV
+    if _LIB_MV is None:
+        import glob
+
+        src = os.path.join(HERE, "emul", "emul_mv.cpp")
+        out = os.path.join(HERE, "emul", "libodef_emul_mv.so")
+        deps = [src, os.path.join(HERE, "emul", "emul.cpp")] + glob.glob(os.path.join(ROOT, "odefilters.jl_amd", "csrc", "*.h"))
+        if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
+            subprocess.check_call(["g++", "-O1", "-std=c++20", "-shared", "-fPIC", "-Wno-unknown-pragmas", src, "-o", out])
+        _LIB_MV = C.CDLL(out)
+        _LIB_MV.emul_precond_fill.argtypes = [C.c_int, C.c_double, C.c_double, dp]
+    return _LIB_MV
+
+
+def emul_solve_mv(rhs_id, d, q, u0s, p, tgrid, model, lag=False):
+    """EK0 with an MV diffusion model ("dynamicMV" / "fixedMV") on a fixed grid, every step saved: the lane filter (lag: lagged
+    record stores), for "fixedMV" the library's postamble (api.hip scale_cov_mv_kernel: entry ((J, a), (K, b)) of every covariance
+    times sqrt(s_a) sqrt(s_b) of the final diffusions, every diffusion record the final one, log-likelihood NaN) restated record
+    by record, then the MV row-team smoother.  Trajectory-major like emul_solve; diff is [N, n_save, d]."""
+    u0s = np.asarray(u0s, float)
+    N, D = u0s.shape[0], d * (q + 1)
+    TRI = D * (D + 1) // 2
+    L = lib_mv()
+    At, Qt, QLt = prior_tables(q)
+    u0_dev = np.ascontiguousarray(u0s.T)
+    p = np.ascontiguousarray(np.asarray(p, float)) if len(p) else np.zeros(1)
+    tg = np.ascontiguousarray(np.asarray(tgrid, float))
+    hs = np.ascontiguousarray(np.diff(tg))
+    nsteps, n_save = len(hs), len(tg)
+    uniq, inv = np.unique(hs, return_inverse=True)
+    ptab = np.zeros((len(uniq), L.emul_tab_stride()))
+    for k, h in enumerate(uniq):
+        L.emul_precond_fill(q, float(h), float(h) ** (-q - 1 / 2), _p(ptab[k]))
+    tab_idx = np.ascontiguousarray(inv.astype(np.int32))
+    ctrl = np.zeros(10)
+    a = EmulArgs()
+    a.rhs, a.q, a.ek1, a.adaptive = rhs_id, q, 0, 0
+    a.N, a.u0, a.p, a.p_shared = N, _p(u0_dev), _p(p), 1
+    a.At, a.Qt, a.QLt = _p(At), _p(Qt), _p(QLt)
+    a.hs, a.ptab, a.tab_idx, a.nsteps = _p(hs), _p(ptab), _p(tab_idx, ip), nsteps
+    a.t0, a.ctrl, a.max_save = float(tg[0]), _p(ctrl), n_save
+    a.everystep, a.fixed_diffusion, a.want_loglik = 1, {"dynamicMV": 3, "fixedMV": 4}[model], 1
+    mean = np.zeros((n_save, D, N)); cov = np.zeros((n_save, TRI, N)); diff = np.zeros((n_save, d, N))
+    tsave = np.zeros((n_save, N)); loglik = np.zeros(N)
+    ints = [np.zeros(N, np.int32) for _ in range(6)]
+    a.mean, a.cov, a.diff, a.tsave, a.loglik = _p(mean), _p(cov), _p(diff), _p(tsave), _p(loglik)
+    a.naccept, a.nreject, a.nf, a.njac, a.nsaved, a.retcode = [_p(x, ip) for x in ints]
+    rc = L.emul_filter_mv(C.byref(a), int(lag))
+    assert rc == 0, rc
+    if model == "fixedMV":
+        fin = diff[n_save - 1].copy()  # [d, N]
+        rs = np.sqrt(fin)
+        k = 0
+        for r in range(D):
+            for c in range(r + 1):
+                cov[:, k, :] *= (rs[r % d] * rs[c % d])[None, :]
+                k += 1
+        diff[1:] = fin[None]
+        loglik[:] = np.nan
+    smean = np.zeros_like(mean); scov = np.zeros_like(cov)
+    a.smean, a.scov, a.n_save = _p(smean), _p(scov), n_save
+    rc = L.emul_smooth_mv(C.byref(a), d)
+    assert rc == 0, rc
+    return dict(mean=mean.transpose(2, 0, 1), cov=unpack_tril(cov.transpose(2, 0, 1), D), diff=diff.transpose(2, 0, 1), loglik=loglik,
+                smean=smean.transpose(2, 0, 1), scov=unpack_tril(scov.transpose(2, 0, 1), D), naccept=ints[0], retcode=ints[5])

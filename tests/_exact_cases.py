@@ -1,6 +1,6 @@
-"""The cases of the extended-precision fixtures of `make_exact.py --small`, and which kernel families the launchers can select
-for each: shared by the generator (tests/golden/make_exact.py), the emulation tests (test_exact_emul.py), the GPU tests
-(test_gpu_exact.py) and tools/exact_ratios.py."""
+"""The cases of the extended-precision fixtures of `make_exact.py --small` and `--models`, and which kernel families the launchers
+can select for each: shared by the generator (tests/golden/make_exact.py), the emulation tests (test_exact_emul.py,
+test_exact_models_emul.py), the GPU tests (test_gpu_exact.py, test_gpu_exact_models.py) and tools/exact_ratios.py."""
 import os
 
 import numpy as np
@@ -33,6 +33,67 @@ RHS_STRUCT = {"fhn": "RhsFHN", "lotka_volterra": "RhsLotkaVolterra", "vanderpol"
 # Lorenz-96 (d = 16) on the matrix-core kernels: the cases, step and ensemble of tests/test_gpu_parity.py
 # test_lorenz96_on_the_matrix_core_kernels (12 steps of dt = 2^-7, trajectories 0 and 5 of 6)
 LORENZ96_CASES = [("EK1", 2), ("EK1", 3), ("EK0", 3), ("EK1", 5)]
+
+
+# The families that have kernels, launch paths or arithmetic of their own beside the ones above (make_exact.py --models): family,
+# field, method, order, diffusion model, step.  The layout of the small fixtures (4 trajectories, 64 steps, covariances of every
+# record); MV diffusions are [traj, step, d].  "map": the on-line MAP update of the global diffusion (ek_math.h, fixed_diffusion
+# == 2).  "mv": the diagonal models of EK0 (filter_fixed_lane<..., MV = true>, rts_smooth_mv_kernel, fixed_diffusion == 3 / 4).
+# "ieks": the THIRD iteration of solve_ieks, each iteration linearised at the previous one's smoothed u as a float64 record.
+# "forced": the time-dependent field of tests/_time_reference.py on the save times t0 + np.arange(65) * dt, t0 = 0.25.
+# Not admissible (the oracle's diffusions further than 1e-4 from the extended-precision ones): see DESIGN.md section 4.
+MODEL_T0 = 0.25
+MODEL_CASES = [
+    ("map", "lotka_volterra", "EK1", 2, "fixedMAP", 2.0**-7),
+    ("map", "lorenz63", "EK1", 3, "fixedMAP", 2.0**-8),
+    ("map", "vanderpol", "EK0", 5, "fixedMAP", 2.0**-6),
+    ("mv", "fhn", "EK0", 1, "dynamicMV", 2.0**-7),
+    ("mv", "lorenz63", "EK0", 3, "dynamicMV", 2.0**-8),
+    ("mv", "vanderpol", "EK0", 5, "dynamicMV", 2.0**-6),
+    ("mv", "lorenz63", "EK0", 3, "fixedMV", 2.0**-8),
+    ("mv", "fhn", "EK0", 3, "fixedMV", 2.0**-7),
+    ("mv", "lotka_volterra", "EK0", 5, "fixedMV", 2.0**-6),
+    ("forced", "forced", "EK0", 2, "dynamic", 2.0**-6),
+    ("forced", "forced", "EK1", 3, "dynamic", 2.0**-6),
+    ("forced", "forced", "EK1", 1, "dynamic", 2.0**-6),
+    ("ieks", "lorenz63", "EK1", 3, "dynamic", 2.0**-8),
+    ("ieks", "lotka_volterra", "EK1", 2, "fixed", 2.0**-7),
+    ("ieks", "vanderpol", "EK1", 4, "fixedMAP", 2.0**-7),
+]
+MODEL_DIM = {**SMALL_DIM, "forced": 2}
+MODEL_RHS_STRUCT = {**RHS_STRUCT, "forced": "RhsForced"}
+IEKS_ITERATIONS = 3
+
+
+def model_cases(family):
+    return [c for c in MODEL_CASES if c[0] == family]
+
+
+def model_id(case):
+    family, rhs, kind, q, diffusion, _ = case
+    return f"{'ieks-' if family == 'ieks' else ''}{rhs}-{kind}{q}" + ("" if diffusion == "dynamic" else "-" + diffusion)
+
+
+def model_name(case):
+    family, rhs, kind, q, diffusion, _ = case
+    return (f"exact_model_{'ieks_' if family == 'ieks' else ''}{rhs}_{kind.lower()}q{q}"
+            f"{'' if diffusion == 'dynamic' else '_' + diffusion.lower()}_ld")
+
+
+def model_grid(case):
+    """The documented save times of a MODEL_CASES fixture."""
+    return (MODEL_T0 if case[0] == "forced" else 0.0) + np.arange(SMALL_NSTEPS + 1) * case[5]
+
+
+def model_field(case):
+    """The oracle's vector field of a case (`forced` lives in tests/_time_reference.py)."""
+    import odefilter_oracle as orc
+
+    if case[1] == "forced":
+        import _time_reference as tr
+
+        return tr.forced()
+    return orc.vector_field(case[1])
 
 
 def case_id(case):

@@ -14,7 +14,10 @@ section 4): lane kernels 1.3-2.0, row-team kernels 0.4-9.7, tiled D = 168 kernel
 orders 1 ... 5, EK0, the fixed diffusion model) and Lorenz-96 on the matrix cores have extended-precision fixtures of their own
 (make_exact.py --small) and `check_against_exact_floored`, the same bar with a floor of one rounding per step: measured 0.6-8.6.
 
-Elsewhere (adaptive solves, fixedMAP, the MV models, IEKS, run-time compiled fields) the tolerance is calibrated on the oracle itself: `noise` = spread of the oracle under 1-ulp input
+fixedMAP, the MV diffusion models, IEKS and the time-dependent field `forced` have such fixtures too (make_exact.py --models,
+tests/test_exact_models_emul.py, tests/test_gpu_exact_models.py).
+
+Elsewhere (adaptive solves, run-time compiled fields) the tolerance is calibrated on the oracle itself: `noise` = spread of the oracle under 1-ulp input
 perturbations, and two fp64 implementations are required to agree within NOISE_FACTOR x noise (+ a 1e-11 floor).
 How the factor relates to the exact fixtures: on Lorenz-63 the oracle's 1-ulp spread is 2x its distance from the exact
 result, so a device 12x as far from exact as the oracle is sits at most (12 + 1) / 2 = 6.5 noise units from the oracle.
@@ -136,8 +139,9 @@ def check_against_exact_floored(fx, k, mean_f, cov_f, mean_s, cov_s, d, diffusio
 
     The floor is one rounding per step: at order 1 the oracle itself is a few ulps from the exact result (4e-15), and a
     kernel that rounds in another order is not 16 x worse for being 20 ulps away after 64 steps.  The solution block is held to
-    U_RTOL as well.  diffusions [n_steps] and loglik, when given, are held to the same form relative to their magnitude (the
-    fixture's oracle_diffusion_err / oracle_loglik_err).  Returns the ratios error / yardstick: {"filt": (per block, cov),
+    U_RTOL as well.  diffusions [n_steps] (the MV diffusion models: [n_steps, d], every entry relative to its own exact value) and
+    loglik, when given, are held to the same form relative to their magnitude (the fixture's oracle_diffusion_err /
+    oracle_loglik_err).  Returns the ratios error / yardstick: {"filt": (per block, cov),
     "smooth": (per block, cov), "diffusion": r, "loglik": r}."""
     D = mean_f.shape[-1]
     il = np.tril_indices(D)
@@ -163,6 +167,7 @@ def check_against_exact_floored(fx, k, mean_f, cov_f, mean_s, cov_s, d, diffusio
         out[name] = (be / yard, ce / cyard)
     if diffusions is not None:
         ex = fx["diffusions"][k]
+        assert np.shape(diffusions) == ex.shape, f"{what}: diffusions of shape {np.shape(diffusions)}, the fixture's are {ex.shape}"
         de = float(np.max(np.abs(np.asarray(diffusions) - ex) / np.abs(ex)))
         dyard = max(float(np.max(fx["oracle_diffusion_err"])), floor)
         assert de <= EXACT_FACTOR * dyard, f"{what}: diffusions off by {de:.2e} relative from the exact ones, {EXACT_FACTOR} x the oracle's distance (floored) is {EXACT_FACTOR * dyard:.2e}"
@@ -174,3 +179,14 @@ def check_against_exact_floored(fx, k, mean_f, cov_f, mean_s, cov_s, d, diffusio
         assert le <= EXACT_FACTOR * lyard, f"{what}: log-likelihood off by {le:.2e} relative from the exact one, {EXACT_FACTOR} x the oracle's distance (floored) is {EXACT_FACTOR * lyard:.2e}"
         out["loglik"] = le / lyard
     return out
+
+
+def check_initial_record_floored(fx, k, mean_f, d, what):
+    """Record 0 on its own: blocks 1 ... q of the Taylor-mode initialisation, which for f(u, p, t) carry the time jet [t0, 1, 0, ...].
+    The bar of the blocks over the run, relative to the record's own block magnitudes: the recursion is a few dozen operations,
+    so the floor of one rounding per step of the run is a generous yardstick for it."""
+    floor = int(fx["nsteps"]) * 2.0**-52
+    be = block_err(mean_f[:1], fx["mean_filt"][k][:1], d)
+    yard = np.maximum(fx["oracle_block_err_filt"].max(axis=0), floor)
+    assert np.all(be <= EXACT_FACTOR * yard), f"{what}: blocks of the initial record off by {be} from the exact ones, bar {EXACT_FACTOR} x {yard}"
+    return be / yard

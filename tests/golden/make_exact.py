@@ -27,6 +27,13 @@ exact result there).  So "the device agrees with the oracle to x" is the wrong q
                          Lorenz-96 (d = 16) on the matrix-core kernels, 12 steps of dt = 2^-7, trajectories 0 and 5, the layout
                          of the Pleiades fixtures
 
+  exact_model_[ieks_]<field>_<ek0|ek1>q<order>[_<model>]_ld.npz  (python tests/golden/make_exact.py --models)
+                         the families with arithmetic of their own, in the layout of the small fixtures (_exact_cases.MODEL_CASES):
+                         the `fixedMAP` diffusion model, the diagonal models `dynamicMV` / `fixedMV` of EK0 (d diffusions per step,
+                         [traj, step, d]), the third iteration of solve_ieks, and the time-dependent field `forced` from t0 = 0.25
+                         (tests/_time_reference.py); the float64 side of the yardstick is orc.solve, tests/_mv_reference.py and
+                         tests/_ieks_reference.py
+
 and, next to them, the float64 oracle's distance from them per derivative block and for the covariance.  Any
 mathematically equivalent formulation gives the same exact result, so the recursion is written in the plain covariance
 form (Sigma^- = A Sigma A' + sigma^2 Q, K = Sigma^- H' S^-1, Sigma = (I - K H) Sigma^- (I - K H)'; G = Sigma A' (Sigma^-)^-1)
@@ -35,10 +42,12 @@ rounding errors by ~6x per step on this problem and is useless after 60 steps.)
 
 A fixture is only as sharp as the oracle's diffusion estimates are: where the residuals are rounding noise in float64 (Pleiades
 order 5 at dt = 2^-10: 0.4 relative and worse) "the oracle's distance" is a lottery ticket.  The --small entry asserts the
-admission condition max |sigma^2_oracle - sigma^2_exact| / sigma^2_exact <= 1e-4 for every fixture trajectory before it writes.
+admission condition max |sigma^2_oracle - sigma^2_exact| / sigma^2_exact <= 1e-4 for every fixture trajectory before it writes,
+and so does --models (for the MV models: every component).
 
 Run (build container, ~3 min):  python tests/golden/make_exact.py            the Lorenz-63 / Pleiades fixtures
                   (~1 min):     python tests/golden/make_exact.py --small    the small-state and Lorenz-96 fixtures
+                  (~10 s):      python tests/golden/make_exact.py --models   fixedMAP, the MV models, IEKS, f(u, p, t)
 """
 import math
 import os
@@ -51,6 +60,9 @@ sys.path.insert(0, os.path.join(HERE, "..", "..", "oracle"))
 sys.path.insert(0, os.path.join(HERE, ".."))
 import odefilter_oracle as orc  # noqa: E402
 from _parity import block_err, cov_err  # noqa: E402
+import _exact_cases as X  # noqa: E402
+import _ieks_reference as ier  # noqa: E402
+import _mv_reference as mvr  # noqa: E402
 from _exact_cases import LORENZ96_CASES, SMALL_CASES, SMALL_NSTEPS, SMALL_NTRAJ, lorenz96_name, small_name  # noqa: E402
 
 
@@ -253,20 +265,21 @@ def lorenz96_jac_ld(u):
     return J
 
 
-def jac_ld(vf, u, p):
-    """The field's Jacobian on longdouble arguments.  The oracle's own `vf.jac` where it builds the matrix from its arguments
+def jac_ld(vf, u, p, t=0.0):
+    """The field's Jacobian on longdouble arguments (and, for f(u, p, t), at the longdouble time t).  The oracle's own `vf.jac` where it builds the matrix from its arguments
     (np.array of longdouble entries stays longdouble; parameters enter as their float64 values, so that 1.0 / c and the like are
     the oracle's); restated where it rounds them into a float64 array (Pleiades, Lorenz-96)."""
     if vf.name == "pleiades":
         return pleiades_jac_ld(u)
     if vf.name == "lorenz96":
         return lorenz96_jac_ld(u)
-    J = np.asarray(vf.jac(u, p, 0.0))
+    J = np.asarray(vf.jac(u, p, t))
     assert J.dtype == np.longdouble or vf.name == "linear", (vf.name, J.dtype)  # linear: the constant diag(p), exact in float64
     return J.astype(np.longdouble)
 
 
-def filter_ld(vf, u0, q, dt, nsteps, kind="EK1", with_smoother=False, diffusion="dynamic", tgrid=None, full=False):
+def filter_ld(vf, u0, q, dt, nsteps, kind="EK1", with_smoother=False, diffusion="dynamic", tgrid=None, full=False, t0=None,
+              linearize_at=None):
     """Any oracle vector field (`vf.f` is written for any scalar type, the Jacobian comes from jac_ld; the parameters are handed
     over as their float64 values).  EK0 / EK1 filter and, if asked, the RTS pass (src/smoothing.jl:4-63) over the same records,
     all in longdouble.  diffusion = "dynamic" (src/diffusions.jl:72-80), or "fixed" (src/diffusions.jl:11-36 in the static order of
@@ -275,15 +288,44 @@ def filter_ld(vf, u0, q, dt, nsteps, kind="EK1", with_smoother=False, diffusion=
     step of the RTS pass).  tgrid: the save times (float64; step n is the float64 difference tgrid[n+1] - tgrid[n], as on every
     other side); without it nsteps steps of dt.  Returns float64 copies: (means, covs) or (means, covs, smoothed means, smoothed
     covs, diffusions); full=True: a dict of those and the log-likelihood sum -(z' S^-1 z + log det S + d log 2 pi) / 2
-    (src/perform_step.jl:66; NaN for "fixed", src/integrator_utils.jl:6)."""
+    (src/perform_step.jl:66; NaN for "fixed", src/integrator_utils.jl:6).
+
+    The other diffusion models (make_exact.py --models):
+      "fixedMAP"   the static order of "fixed" with the on-line mode of the InverseGamma(1/2, 1/2) posterior in place of the running
+                   mean (src/diffusions.jl:46-68 as the oracle's perform_step writes it, n_obs = n + 1); log-likelihood NaN.
+      "dynamicMV"  EK0; sigma_a = max(z_a^2 / (H Q H')_00, eps_float64), Sigma^- = A X A' + D^1/2 Q D^1/2 with
+                   D = kron(I_{q+1}, diag sigma) (src/diffusions.jl:83-112; tests/_mv_reference.py apply_diffusion on the covariance
+                   instead of the factor); the log-likelihood is accumulated.
+      "fixedMV"    EK0; predicts with the unscaled Q, local_a = z_a^2 / S_00 -- the FIRST diagonal entry of S for every component,
+                   as the reference (src/diffusions.jl:115-153) --, running mean per component; the postamble rescales every
+                   covariance to D^1/2 Sigma D^1/2 with the final vector; log-likelihood NaN.
+    With an MV model the diffusions are [nsteps, d] and the RTS pass uses D^1/2 Q D^1/2 of the step.
+    t0: the absolute start time of a field f(u, p, t) (needs tgrid, whose first entry it is): the step evaluates f and the Jacobian
+    at tgrid[n + 1] as longdouble, and the Taylor-mode initialisation hands f the jet [t0, 1, 0, ...] (the longdouble twin of
+    tests/_time_reference.py time_field).  Without it every evaluation gets t = 0.0, as before.
+    linearize_at [n_t, d] float64: the EK1 Jacobian of the step ending at tgrid[k] is evaluated at linearize_at[k] (one IEKS
+    iteration, tests/_ieks_reference.py); the residual keeps f(u_pred)."""
     ld = np.longdouble
     d, NB = vf.d, q + 1
     D = d * NB
     p = vf.p
+    mv = diffusion in ("dynamicMV", "fixedMV")
+    assert diffusion in ("dynamic", "fixed", "fixedMAP", "dynamicMV", "fixedMV"), diffusion
+    assert not mv or kind == "EK0", "the MV diffusion models require EK0"
+    assert linearize_at is None or kind == "EK1"
+    if t0 is not None:
+        assert tgrid is not None and float(tgrid[0]) == float(t0)
+        tjet = np.zeros(NB, dtype=ld)
+        tjet[0] = ld(t0)
+        if NB > 1:
+            tjet[1] = 1
+        t_init = JetLD(tjet)
+    else:
+        t_init = 0.0
     coef = np.zeros((d, NB), dtype=ld)
     coef[:, 0] = np.asarray(u0, dtype=ld)
     for k in range(q):  # Taylor-mode initial state (src/state_initialization.jl:15-42) in longdouble
-        fu = vf.f([JetLD(coef[i].copy()) for i in range(d)], p, 0.0)
+        fu = vf.f([JetLD(coef[i].copy()) for i in range(d)], p, t_init)
         for i in range(d):
             coef[i, k + 1] = JetLD.lift(fu[i], NB).c[k] / (k + 1)
     m = np.concatenate([coef[:, k] * ld(math.factorial(k)) for k in range(NB)])
@@ -310,34 +352,58 @@ def filter_ld(vf, u0, q, dt, nsteps, kind="EK1", with_smoother=False, diffusion=
     for h in hs:
         if float(h) not in Ps:
             Ps[float(h)] = precond(h)
+    def scaled_q(s2):
+        """sigma^2 Q, or D^1/2 Q D^1/2 for a vector of d diffusions."""
+        if np.ndim(s2) == 0:
+            return s2 * Q
+        r = np.tile(np.sqrt(np.asarray(s2, dtype=ld)), NB)
+        return np.outer(r, r) * Q
+
+    static = diffusion in ("fixed", "fixedMAP", "fixedMV")
     S_ = np.zeros((D, D), dtype=ld)
     means, covs, diffs = [m.copy()], [S_.copy()], []
     loglik, gdiff = ld(0), None
     for n in range(nsteps):
         P = Ps[float(hs[n])]
         PI = ld(1) / P
+        tn = 0.0 if t0 is None else ld(np.float64(tgrid[n + 1]))
         mt, X = P * m, S_ * np.outer(P, P)
         mp_ = A @ mt
         up = (PI * mp_)[:d]
-        du = np.asarray(vf.f(list(up), p, 0.0), dtype=ld)
+        du = np.asarray(vf.f(list(up), p, tn), dtype=ld)
         z = (PI * mp_)[d:2 * d] - du
         H = np.zeros((d, D), dtype=ld)
         if kind == "EK1":
-            H[:, :d] = -jac_ld(vf, up, p) * PI[:d][None, :]
+            ulin = up if linearize_at is None else np.asarray(linearize_at[n + 1], dtype=np.float64).astype(ld)
+            H[:, :d] = -jac_ld(vf, ulin, p, tn) * PI[:d][None, :]
         H[:, d:2 * d] = np.diag(PI[d:2 * d])
         if diffusion == "dynamic":
             W = H @ Q @ H.T
             s2 = (z @ solve_spd_ld(W, z[:, None])[:, 0]) / d
             Xp = A @ X @ A.T + s2 * Q
+        elif diffusion == "dynamicMV":
+            s2 = np.maximum(z * z / (H @ Q @ H.T)[0, 0], ld(np.finfo(np.float64).eps))
+            Xp = A @ X @ A.T + scaled_q(s2)
         else:
-            assert diffusion == "fixed", diffusion
             Xp = A @ X @ A.T + Q
         C = Xp @ H.T
         Sm = H @ C
         K = solve_spd_ld(Sm, C.T).T
-        if diffusion == "fixed":  # oracle perform_step: success_iter = number of accepted steps so far
+        if diffusion in ("fixed", "fixedMAP"):  # oracle perform_step: success_iter = number of accepted steps so far
             dtn = (z @ solve_spd_ld(Sm, z[:, None])[:, 0]) / d
-            gdiff = dtn if n == 0 else gdiff + (dtn - gdiff) / n
+            if diffusion == "fixed":
+                gdiff = dtn if n == 0 else gdiff + (dtn - gdiff) / n
+            else:  # mode of the InverseGamma(1/2, 1/2) posterior, on-line (oracle/odefilter_oracle.py perform_step)
+                n_obs, alpha, beta, half = n + 1, ld(0.5), ld(0.5), ld(0.5)
+                if n == 0:
+                    gdiff = (beta + half * dtn) / (alpha + ld(n_obs * d) / 2 + 1)
+                else:
+                    res_prev = (gdiff * (alpha + ld((n_obs - 1) * d) / 2 + 1) - beta) * 2
+                    gdiff = (beta + half * (res_prev + dtn)) / (alpha + ld(n_obs * d) / 2 + 1)
+            s2 = gdiff
+        elif diffusion == "fixedMV":
+            local = z * z / Sm[0, 0]
+            gdiff = local if n == 0 else gdiff + (local - gdiff) / n
             s2 = gdiff
         elif full:
             Lc = chol_ld(Sm)
@@ -348,8 +414,12 @@ def filter_ld(vf, u0, q, dt, nsteps, kind="EK1", with_smoother=False, diffusion=
         Xf = (Xf + Xf.T) / 2
         m, S_ = PI * mf, Xf * np.outer(PI, PI)
         means.append(m.copy()); covs.append(S_.copy()); diffs.append(s2)
-    if diffusion == "fixed":  # postamble
-        covs = [c * gdiff for c in covs]
+    if static:  # postamble
+        if diffusion == "fixedMV":
+            r = np.tile(np.sqrt(gdiff), NB)
+            covs = [c * np.outer(r, r) for c in covs]
+        else:
+            covs = [c * gdiff for c in covs]
         diffs = [gdiff for _ in diffs]
         loglik = ld(np.nan)
     f64 = lambda a: np.array(a).astype(np.float64)  # noqa: E731
@@ -365,7 +435,7 @@ def filter_ld(vf, u0, q, dt, nsteps, kind="EK1", with_smoother=False, diffusion=
         PI = ld(1) / P
         PP = np.outer(P, P)
         mt, X = P * means[i], covs[i] * PP
-        B = A @ X @ A.T + diffs[i] * Q
+        B = A @ X @ A.T + scaled_q(diffs[i])
         B = (B + B.T) / 2
         G = solve_spd_ld(B, A @ X).T  # X A' B^-1 (X, B symmetric)
         ms_ = mt + G @ (P * sm[i + 1] - A @ mt)
@@ -453,6 +523,55 @@ def small_fixture(rhs, kind, q, diffusion, dt, nsteps=SMALL_NSTEPS, ntraj=SMALL_
     return out
 
 
+def model_fixture(case, nsteps=SMALL_NSTEPS, ntraj=SMALL_NTRAJ):
+    """A MODEL_CASES fixture in the layout of small_fixture.  The float64 side of the yardstick: orc.solve ("map", "forced"),
+    tests/_mv_reference.py solve ("mv"), tests/_ieks_reference.py solve_ieks running its own chain of IEKS_ITERATIONS iterations
+    ("ieks"; the extended-precision chain linearises iteration j at the float64 rounding of its own iteration j - 1's smoothed u,
+    as a device reads it back from a float64 record)."""
+    family, rhs, kind, q, diffusion, dt = case
+    vf = X.model_field(case)
+    u0s = orc.ensemble_u0(vf.u0, ntraj, 1e-2)
+    tg = X.model_grid(case)[: nsteps + 1]
+    t0 = X.MODEL_T0 if family == "forced" else None
+    d = vf.d
+    il = np.tril_indices(d * (q + 1))
+    with_loglik = diffusion in ("dynamic", "dynamicMV")
+    out = dict(family=family, rhs=rhs, kind=kind, order=q, ek1=int(kind == "EK1"), diffusionmodel=diffusion, dt=dt, nsteps=nsteps, t=tg,
+               trajs=np.arange(ntraj), u0s=u0s)
+    if family == "ieks":
+        out["iterations"] = X.IEKS_ITERATIONS
+    acc = {k: [] for k in ("mean_filt", "mean_smooth", "cov_filt_tril", "cov_smooth_tril", "diffusions", "loglik",
+                           "oracle_block_err_filt", "oracle_block_err_smooth", "oracle_cov_err_filt", "oracle_cov_err_smooth",
+                           "oracle_diffusion_err", "oracle_loglik_err")}
+    for i in range(ntraj):
+        kw = dict(kind=kind, with_smoother=True, diffusion=diffusion, tgrid=tg, full=True, t0=t0)
+        if family == "ieks":
+            lin = None
+            for _ in range(X.IEKS_ITERATIONS):
+                r = filter_ld(vf, u0s[i], q, dt, nsteps, linearize_at=lin, **kw)
+                lin = r["mean_smooth"][:, :d]
+            sol = ier.solve_ieks(vf, q, diffusion, tg, X.IEKS_ITERATIONS, u0=u0s[i])
+        else:
+            r = filter_ld(vf, u0s[i], q, dt, nsteps, **kw)
+            if family == "mv":
+                sol = mvr.solve(vf, diffusion, q, u0=u0s[i], tspan=(tg[0], tg[-1]), tgrid=tg)
+            else:
+                sol = orc.solve(vf, orc.Alg(kind, q, diffusion, True), u0=u0s[i], tspan=(tg[0], tg[-1]), tgrid=tg)
+        assert len(sol.t) == nsteps + 1 and sol.retcode == "Success"
+        for name, sm in (("filt", False), ("smooth", True)):
+            acc["mean_" + name].append(r["mean_" + name])
+            acc[f"cov_{name}_tril"].append(r["cov_" + name][:, il[0], il[1]])
+            acc["oracle_block_err_" + name].append(block_err(sol.means(smoothed=sm), r["mean_" + name], d))
+            acc["oracle_cov_err_" + name].append(cov_err(sol.covs(smoothed=sm)[1:], r["cov_" + name][1:]))  # record 0: zero
+        acc["diffusions"].append(r["diffusions"]); acc["loglik"].append(r["loglik"])
+        od = np.asarray(sol.diffusions, float)
+        assert od.shape == r["diffusions"].shape, (od.shape, r["diffusions"].shape)
+        acc["oracle_diffusion_err"].append(float(np.max(np.abs(od - r["diffusions"]) / np.abs(r["diffusions"]))))  # MV: per component
+        acc["oracle_loglik_err"].append(abs(sol.log_likelihood - r["loglik"]) / abs(r["loglik"]) if with_loglik else np.nan)
+    out.update({k: np.array(v) for k, v in acc.items()})
+    return out
+
+
 def admit(name, fx):
     worst = float(np.max(fx["oracle_diffusion_err"]))
     assert worst <= ADMIT_DIFFUSION_ERR, (f"{name}: the oracle's diffusions are {worst:.1e} relative off the extended-precision ones "
@@ -488,9 +607,24 @@ def main_small():
               "| diffusions", fx["oracle_diffusion_err"], "loglik", fx["oracle_loglik_err"], flush=True)
 
 
+def main_models(cases=None):
+    for case in (X.MODEL_CASES if cases is None else cases):
+        name = X.model_name(case)
+        fx = model_fixture(case)
+        admit(name, fx)
+        wrote = write_if_changed(os.path.join(HERE, name + ".npz"), fx)
+        print(name, "(written)" if wrote else "(unchanged)", ": oracle vs extended precision, filter blocks", fx["oracle_block_err_filt"].max(axis=0),
+              "cov", fx["oracle_cov_err_filt"].max(), "| smoother blocks", fx["oracle_block_err_smooth"].max(axis=0), "cov",
+              fx["oracle_cov_err_smooth"].max(), "| diffusions", fx["oracle_diffusion_err"].max(), "loglik", np.nanmax(fx["oracle_loglik_err"])
+              if np.isfinite(fx["oracle_loglik_err"]).any() else np.nan, flush=True)
+
+
 if __name__ == "__main__":
     if "--small" in sys.argv[1:]:
         main_small()
+        sys.exit(0)
+    if "--models" in sys.argv[1:]:
+        main_models()
         sys.exit(0)
     vf = orc.vector_field("lorenz63")
     u0 = orc.ensemble_u0(vf.u0, 1, 1e-2)[0]

@@ -7,6 +7,8 @@ per fixture and kernel combination -- the numbers behind the factor-16 bar of te
 exact_lorenz96_*_smooth_ld.npz): every kernel family the launchers can select, through the C ABI as tests/test_gpu_exact.py runs
 them; ratios are error / max(oracle's distance, n_steps 2^-52), the largest over the checked trajectories
 (check_against_exact_floored).  --small-emul: the host build of the device source instead (tests/test_exact_emul.py; no GPU).
+--models / --models-emul: the same for fixedMAP, the MV diffusion models, IEKS and the time-dependent field `forced`
+(tests/golden/exact_model_*_ld.npz; tests/test_gpu_exact_models.py / tests/test_exact_models_emul.py).
 Each line carries "source": "device" or "emulation" and the oracle's distances the ratios are measured in."""
 import json, os, sys
 import numpy as np
@@ -50,6 +52,52 @@ def small_lines(source):
             emit(f"lorenz96-{kind}{q}", f"mfma+{smoother}", fx, lambda: G.check_lorenz96(fx, sol, kind, q, smoother))
 
 
+def model_lines(source):
+    import _exact_cases as X
+
+    def emit(case, kernels, run):
+        fx = X.load(X.model_name(case))
+        out = {"fixture": X.model_id(case), "family": case[0], "kernels": kernels, "source": source, "oracle_distance": X.oracle_distance(fx)}
+        try:
+            out.update(X.worst_of([X.ratio_record(r) for r in run()]))
+        except AssertionError as e:  # a ratio above the bar: the message carries the figures
+            out["failed"] = str(e).splitlines()[0]
+        print(json.dumps(out), flush=True)
+
+    if source == "emulation":
+        import test_exact_models_emul as T
+
+        for case in X.MODEL_CASES:
+            for kernels in T.emul_kernels(case):
+                emit(case, kernels, lambda: T.check_emulation(case, kernels))
+        return
+    import pytest
+    import odefilters_jl_amd as pkg
+    import test_gpu_exact_models as G
+
+    mp = pytest.MonkeyPatch()
+    for case, filt, smoother in G.MAP_COMBOS:
+        with mp.context() as m:
+            fx, sol = G.solve_map(pkg, case, filt, smoother, m.setenv)
+            emit(case, f"{filt}+{smoother}", lambda: G.check_map(fx, sol, case, filt, smoother))
+    for case, filt in G.MV_COMBOS:
+        with mp.context() as m:
+            fx, sol = G.solve_mv(pkg, case, filt, m.setenv)
+            emit(case, f"{filt}+mv", lambda: G.check_mv(fx, sol, case, filt))
+    for case, filt in G.IEKS_COMBOS:
+        with mp.context() as m:
+            fx, sol = G.solve_ieks(pkg, case, filt, m)
+            emit(case, filt, lambda: G.check_ieks(fx, sol, case, filt))
+            sol.ctx.close()
+    for case, filt in G.FORCED_COMBOS:
+        with mp.context() as m:
+            fx, sol = G.solve_forced(pkg, case, filt, m)
+            emit(case, filt, lambda: G.check_forced(fx, sol, case, filt))
+
+
+if "--models" in sys.argv[1:] or "--models-emul" in sys.argv[1:]:
+    model_lines("emulation" if "--models-emul" in sys.argv[1:] else "device")
+    sys.exit(0)
 if "--small" in sys.argv[1:] or "--small-emul" in sys.argv[1:]:
     small_lines("emulation" if "--small-emul" in sys.argv[1:] else "device")
     sys.exit(0)
