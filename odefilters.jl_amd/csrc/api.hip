@@ -476,34 +476,40 @@ int datalik_check(const odef_ctx* c, int, const char* who) {
 // the cached array of a data log-likelihood field; the first request after the records or an input changed runs the pass
 size_t datalik_bytes(const odef_ctx* c, int) { return (size_t)c->cfg.n_traj * sizeof(double); }
 
-// the pass over every trajectory's own records with a node per observation time (ODEF_L_OBS_TIME)
-int datalik_times_ensure(odef_ctx* c, const char* who) {
-  DataLikTimesRequest r;
-  std::memset(&r, 0, sizeof r);
+// the part of a request that both data log-likelihood passes take from the context: the filter records and the observed components
+int datalik_request(odef_ctx* c, const char* who, DataLikObsRequest& r) {
   r.pc = &c->pc;
   r.N = c->cfg.n_traj;
   r.n_save = c->n_save;
   r.d = c->d;
   r.q = c->q;
+  r.mean = (const double*)c->f[ODEF_F_MEAN].ptr;
+  r.cov = (const double*)c->f[ODEF_F_COV_TRIL].ptr;
+  r.diff = (const double*)c->f[ODEF_F_DIFFUSION].ptr;
+  r.obs_comp = c->obs[1].ptr;
+  r.obs_val = (const double*)c->obs[2].ptr;
+  r.obs_noise = (const double*)c->obs[3].ptr;
+  r.comp_bytes = c->obs[1].bytes;
+  r.val_bytes = c->obs[2].bytes;
+  r.noise_bytes = c->obs[3].bytes;
+  if (!r.mean || !r.cov || !r.diff) return fail(c, "%s: the filter records hold no data", who);
+  return 0;
+}
+
+// the pass over every trajectory's own records with a node per observation time (ODEF_L_OBS_TIME)
+int datalik_times_ensure(odef_ctx* c, const char* who) {
+  DataLikTimesRequest r{};
+  if (datalik_request(c, who, r)) return -1;
   r.adaptive = c->adaptive;
   r.t0 = c->adaptive || c->tgrid.empty() ? c->t0 : c->tgrid.front();
   r.t_last = c->tgrid.empty() ? 0.0 : c->tgrid.back();
   r.tgrid = c->d_tgrid;
   r.tsave = (const double*)c->f[ODEF_F_T].ptr;
   r.nsaved = (const int*)c->f[ODEF_F_NSAVED].ptr;
-  r.mean = (const double*)c->f[ODEF_F_MEAN].ptr;
-  r.cov = (const double*)c->f[ODEF_F_COV_TRIL].ptr;
-  r.diff = (const double*)c->f[ODEF_F_DIFFUSION].ptr;
-  if (!r.mean || !r.cov || !r.diff || (c->adaptive ? !r.tsave || !r.nsaved : !r.tgrid || (long)c->tgrid.size() != c->n_save))
+  if (c->adaptive ? !r.tsave || !r.nsaved : !r.tgrid || (long)c->tgrid.size() != c->n_save)
     return fail(c, "%s: the filter records hold no data", who);
   r.obs_time = (const double*)c->obs[4].ptr;
-  r.obs_comp = c->obs[1].ptr;
-  r.obs_val = (const double*)c->obs[2].ptr;
-  r.obs_noise = (const double*)c->obs[3].ptr;
   r.time_bytes = c->obs[4].bytes;
-  r.comp_bytes = c->obs[1].bytes;
-  r.val_bytes = c->obs[2].bytes;
-  r.noise_bytes = c->obs[3].bytes;
   std::string err;
   if (datalik_times_run(c->datalik, r, c->stream, &c->ms[kPassDataLik], &c->nl[kPassDataLik], c->kname[kPassDataLik],
                         sizeof c->kname[kPassDataLik], err))
@@ -515,28 +521,14 @@ int datalik_fetch(odef_ctx* c, int field, const char* who, void** ptr) {
   if (!c->datalik.valid && datalik_by_time(c)) {
     if (datalik_times_ensure(c, who)) return -1;
   } else if (!c->datalik.valid) {
-    DataLikRequest r;
-    std::memset(&r, 0, sizeof r);
-    r.pc = &c->pc;
-    r.N = c->cfg.n_traj;
-    r.n_save = c->n_save;
-    r.d = c->d;
-    r.q = c->q;
+    DataLikRequest r{};
+    if (datalik_request(c, who, r)) return -1;
     r.ptab = c->d_ptab;
     r.tab_idx = c->d_tab_idx;
     r.hs = c->d_hs;
-    r.mean = (const double*)c->f[ODEF_F_MEAN].ptr;
-    r.cov = (const double*)c->f[ODEF_F_COV_TRIL].ptr;
-    r.diff = (const double*)c->f[ODEF_F_DIFFUSION].ptr;
-    if (!r.mean || !r.cov || !r.diff || !r.hs) return fail(c, "%s: the filter records hold no data", who);
+    if (!r.hs) return fail(c, "%s: the filter records hold no data", who);
     r.obs_save = c->obs[0].ptr;
-    r.obs_comp = c->obs[1].ptr;
-    r.obs_val = (const double*)c->obs[2].ptr;
-    r.obs_noise = (const double*)c->obs[3].ptr;
     r.save_bytes = c->obs[0].bytes;
-    r.comp_bytes = c->obs[1].bytes;
-    r.val_bytes = c->obs[2].bytes;
-    r.noise_bytes = c->obs[3].bytes;
     std::string err;
     if (datalik_run(c->datalik, r, c->stream, &c->ms[kPassDataLik], &c->nl[kPassDataLik], c->kname[kPassDataLik],
                     sizeof c->kname[kPassDataLik], err))

@@ -21,21 +21,26 @@ struct DataLikState {
   PassTimer timer;
 };
 
-struct DataLikRequest {
+// what a request says whichever way the observations are placed in time: the filter records and the observed components
+struct DataLikObsRequest {
   const PriorConsts* pc;
-  long N, n_save;
+  long N, n_save;          // fixed grid: number of saves; adaptive: capacity of the records
   int d, q;
-  const double* ptab;   // the grid's tables, as the smoother takes them
-  const int* tab_idx;
-  const double* hs;
-  const double* mean;   // filter records, ABI layout
+  const double* mean;      // filter records, ABI layout
   const double* cov;
   const double* diff;
-  const void* obs_save;    // [M] int64
   const void* obs_comp;    // [o] int64
   const double* obs_val;   // [M][o] or [M][o][N]
   const double* obs_noise; // [o]
-  size_t save_bytes, comp_bytes, val_bytes, noise_bytes;
+  size_t comp_bytes, val_bytes, noise_bytes;
+};
+
+struct DataLikRequest : DataLikObsRequest {
+  const double* ptab;      // the grid's tables, as the smoother takes them
+  const int* tab_idx;
+  const double* hs;
+  const void* obs_save;    // [M] int64
+  size_t save_bytes;
 };
 
 // true when data_loglik_kernel<d, q> is instantiated (d <= 4, q <= 5, d (q + 1) <= 20)
@@ -48,24 +53,15 @@ void datalik_free(DataLikState& st);
 
 // The same likelihood at arbitrary observation times, on fixed and on adaptive grids (datalik_times.hip): the sweep
 // runs over every trajectory's own records plus one predicted node per time that is no save.  Same state, same outputs.
-struct DataLikTimesRequest {
-  const PriorConsts* pc;
-  long N, n_save;          // fixed grid: number of saves; adaptive: capacity of the records
-  int d, q;
+struct DataLikTimesRequest : DataLikObsRequest {
   int adaptive;
   double t0;               // the first save time (of every trajectory)
   double t_last;           // fixed grid: the last save time
   const double* tgrid;     // fixed: [n_save], device
   const double* tsave;     // adaptive: [n_save][N]
   const int* nsaved;       // adaptive: [N]
-  const double* mean;      // filter records, ABI layout
-  const double* cov;
-  const double* diff;
   const double* obs_time;  // [M] doubles
-  const void* obs_comp;    // [o] int64
-  const double* obs_val;   // [M][o] or [M][o][N]
-  const double* obs_noise; // [o]
-  size_t time_bytes, comp_bytes, val_bytes, noise_bytes;
+  size_t time_bytes;
 };
 
 // true when data_loglik_times_kernel<d, q> is instantiated (d <= 4, q <= 5, d (q + 1) <= 12)

@@ -152,14 +152,8 @@ __device__ inline void datalik_load(const double* __restrict__ mean, const doubl
   }
 }
 
-#ifdef ODEF_HOST_EMUL
-#define ODEF_DATALIK_INLINE inline
-#else
-#define ODEF_DATALIK_INLINE __attribute__((always_inline)) inline  // (see the call of rts_step_core below)
-#endif
-
 template <int d, int q>
-__device__ ODEF_DATALIK_INLINE void data_loglik_lane(const DataLikArgs& P, long i0, unsigned lane, const LaneMem& xl) {
+__device__ ODEF_FORCE_INLINE void data_loglik_lane(const DataLikArgs& P, long i0, unsigned lane, const LaneMem& xl) {
   constexpr int NB = q + 1, D = d * NB, TRI = D * (D + 1) / 2;
   static_assert(d <= kDataLikMaxD && D <= kDataLikMaxState, "data log-likelihood: d <= 4, d (q + 1) <= 20");
   const long i = i0 + lane;
@@ -227,10 +221,7 @@ __device__ ODEF_DATALIK_INLINE void data_loglik_lane(const DataLikArgs& P, long 
       auto sink = [&](int e, double v) { B[e] = v; };
       // (forced in line: left to its cost model the compiler keeps the core of the largest states as a function of its own, and no
       // kernel of this library calls one)
-#ifdef __clang__
-      [[clang::always_inline]]
-#endif
-      rts_step_core<d, NB>(P.pc, pij, mt, B, Cs, msn, sigma2, xl, mo, sink);
+      ODEF_INLINE_CALL rts_step_core<d, NB>(P.pc, pij, mt, B, Cs, msn, sigma2, xl, mo, sink);
 #pragma unroll
       for (int e = 0; e < D; ++e) xm[e] = mo[e];
 #pragma unroll

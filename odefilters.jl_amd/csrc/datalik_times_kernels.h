@@ -48,7 +48,7 @@ struct DataLikTimesArgs {
 };
 
 // true when any lane of the wavefront holds b (every lane of the wavefront calls it)
-__device__ ODEF_DATALIK_INLINE bool datalik_wave_any(bool b) {
+__device__ ODEF_FORCE_INLINE bool datalik_wave_any(bool b) {
 #ifdef ODEF_HOST_EMUL
   return b;
 #else
@@ -62,9 +62,9 @@ __device__ ODEF_DATALIK_INLINE bool datalik_wave_any(bool b) {
 // taken.  H = s0 times rows of the identity on the first d coordinates (s0: the un-preconditioning of derivative block 0).  Sums and
 // pivot rule as in datalik_update.
 template <int d, int D>
-__device__ ODEF_DATALIK_INLINE void datalik_update_node(double (&w)[D], double (&W)[D * (D + 1) / 2], const double (&m)[D], const LaneMem& xl,
-                                                        double s0, const int (&slot)[d], const double (&rn)[d], const double (&yv)[d],
-                                                        double& quad, double& logdet, bool& bad) {
+__device__ ODEF_FORCE_INLINE void datalik_update_node(double (&w)[D], double (&W)[D * (D + 1) / 2], const double (&m)[D], const LaneMem& xl,
+                                                      double s0, const int (&slot)[d], const double (&rn)[d], const double (&yv)[d],
+                                                      double& quad, double& logdet, bool& bad) {
   constexpr int td = d * (d + 1) / 2;
   double U[d][D], S[td], v[d], dinv[d];
 #pragma unroll
@@ -168,8 +168,8 @@ __device__ ODEF_DATALIK_INLINE void datalik_update_node(double (&w)[D], double (
 // The sweep of the wavefront's lane `lane` (trajectory i0 + lane).  Every lane of the wavefront calls it, `valid` or not: the save
 // index and the votes are wave-uniform.  A lane that is not valid reads and writes nothing.
 template <int d, int q>
-__device__ ODEF_DATALIK_INLINE void data_loglik_times_lane(const DataLikTimesArgs& P, long i0, unsigned lane, bool valid,
-                                                           const LaneMem& xl) {
+__device__ ODEF_FORCE_INLINE void data_loglik_times_lane(const DataLikTimesArgs& P, long i0, unsigned lane, bool valid,
+                                                         const LaneMem& xl) {
   constexpr int NB = q + 1, D = d * NB, TRI = D * (D + 1) / 2;
   static_assert(d <= kDataLikMaxD && D <= kDataLikTimesMaxState, "data log-likelihood at times: d <= 4, d (q + 1) <= 12");
   const long i = i0 + lane;

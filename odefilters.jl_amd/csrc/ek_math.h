@@ -22,6 +22,20 @@
 #define ODEF_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 #endif
 
+// A device function that has to end up inside its kernel.  Left to its cost model the compiler keeps the RTS step of the largest
+// states as a function of its own, and no kernel of this library calls one (tests/test_build_hygiene.py).  ODEF_INLINE_CALL in
+// front of a statement does the same for the calls in it, where the callee itself is left to the cost model elsewhere.
+#ifdef ODEF_HOST_EMUL
+#define ODEF_FORCE_INLINE inline
+#else
+#define ODEF_FORCE_INLINE __attribute__((always_inline)) inline
+#endif
+#ifdef __clang__
+#define ODEF_INLINE_CALL [[clang::always_inline]]
+#else
+#define ODEF_INLINE_CALL
+#endif
+
 namespace odef {
 
 constexpr int MAXNB = 6;  // order <= 5

@@ -6,49 +6,11 @@
 #include <cstdint>
 #include <cstdio>
 
+#include "dispatch_dq.h"
 #include "events_kernels.h"
 
 namespace odef {
 namespace {
-
-template <int d, int q>
-void launch(const EventArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((event_refine_kernel<d, q>), dim3((unsigned)((a.N + kEventWave - 1) / kEventWave), (unsigned)a.K), dim3(kEventWave),
-                     0, st, a);
-}
-
-template <int d>
-bool launch_order(int q, const EventArgs& a, hipStream_t st) {
-  if (d * (q + 1) > kEventMaxState) return false;
-  switch (q) {
-    case 1: launch<d, 1>(a, st); return true;
-    case 2:
-      if constexpr (d * 3 <= kEventMaxState) {
-        launch<d, 2>(a, st);
-        return true;
-      }
-      return false;
-    case 3:
-      if constexpr (d * 4 <= kEventMaxState) {
-        launch<d, 3>(a, st);
-        return true;
-      }
-      return false;
-    case 4:
-      if constexpr (d * 5 <= kEventMaxState) {
-        launch<d, 4>(a, st);
-        return true;
-      }
-      return false;
-    case 5:
-      if constexpr (d * 6 <= kEventMaxState) {
-        launch<d, 5>(a, st);
-        return true;
-      }
-      return false;
-    default: return false;
-  }
-}
 
 template <class T>
 bool alloc(T*& p, size_t n) {
@@ -66,7 +28,7 @@ void release(EventsCache& ec) {
 
 }  // namespace
 
-bool events_has(int d, int q) { return d >= 1 && d <= kEventMaxD && q >= 1 && q <= 5 && d * (q + 1) <= kEventMaxState; }
+bool events_has(int d, int q) { return has_dq<kEventMaxD, kEventMaxState>(d, q); }
 
 int events_run(EventsState& st, EventsCache& ec, const EventsRequest& r, hipStream_t stream, float* ms, int* n_launches, char* kname,
                size_t kname_n, std::string& err) {
@@ -129,15 +91,11 @@ int events_run(EventsState& st, EventsCache& ec, const EventsRequest& r, hipStre
   a.neval = ec.neval;
   if (st.timer.begin(stream) != hipSuccess) return pass_fail(err, "event location: hipEventCreate failed");
   hipLaunchKernelGGL(event_scan_kernel, dim3((unsigned)((a.N + kEventWave - 1) / kEventWave)), dim3(kEventWave), 0, stream, a);
-  bool ok = false;
-  switch (r.d) {
-    case 1: ok = launch_order<1>(r.q, a, stream); break;
-    case 2: ok = launch_order<2>(r.q, a, stream); break;
-    case 3: ok = launch_order<3>(r.q, a, stream); break;
-    case 4: ok = launch_order<4>(r.q, a, stream); break;
-    default: break;
-  }
-  if (!ok) return pass_fail(err, "event location: no kernel");
+  auto refine = [&]<int d, int q>() {
+    hipLaunchKernelGGL((event_refine_kernel<d, q>), dim3((unsigned)((a.N + kEventWave - 1) / kEventWave), (unsigned)a.K), dim3(kEventWave),
+                       0, stream, a);
+  };
+  if (!dispatch_dq<kEventMaxD, kEventMaxState>(r.d, r.q, refine)) return pass_fail(err, "event location: no kernel");
   if (kname) std::snprintf(kname, kname_n, "odef::event_refine_kernel<%d, %d>", r.d, r.q);
   if (e = st.timer.end(stream, ms); e != hipSuccess) return pass_fail(err, "event location: %s", hipGetErrorString(e));
   if (n_launches) *n_launches += 2;  // a running count: a request served from the cache leaves it unchanged

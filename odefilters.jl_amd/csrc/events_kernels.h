@@ -49,15 +49,9 @@ struct EventArgs {
   int* neval;              // [K][N]
 };
 
-#ifdef ODEF_HOST_EMUL
-#define ODEF_EVENTS_INLINE inline
-#else
-#define ODEF_EVENTS_INLINE __attribute__((always_inline)) inline  // (no kernel of this library calls a function)
-#endif
-
 // The scan of one trajectory.  `n_hi`: wave-uniform upper bound of the record counts of the wavefront (fixed grid: n_save), so that
 // every load of a row is the same save for all lanes: 512 contiguous bytes.
-__device__ ODEF_EVENTS_INLINE void event_scan_lane(const EventArgs& P, long i, long n_hi) {
+__device__ ODEF_FORCE_INLINE void event_scan_lane(const EventArgs& P, long i, long n_hi) {
   const size_t N = (size_t)P.N;
   const long n = P.adaptive ? (long)P.nsaved[i] : P.n_save;
   const double* row = (P.source ? P.smean : P.mean) + (size_t)P.comp * N + (size_t)i;  // save k at row[k D N]
@@ -107,7 +101,7 @@ __device__ ODEF_EVENTS_INLINE void event_scan_lane(const EventArgs& P, long i, l
 
 // entry `c` (a run-time index) of a register array, by selection: every index stays a compile-time constant
 template <int n, int lo, int cnt>
-__device__ ODEF_EVENTS_INLINE double event_pick(const double (&v)[n], int c) {
+__device__ ODEF_FORCE_INLINE double event_pick(const double (&v)[n], int c) {
   double r = v[lo];
 #pragma unroll
   for (int a = 1; a < cnt; ++a) r = (a == c) ? v[lo + a] : r;
@@ -121,8 +115,8 @@ __device__ ODEF_EVENTS_INLINE double event_pick(const double (&v)[n], int c) {
 // `limit` (source 0, mean alone): the prediction itself at t = t_{k+1}, i.e. the left limit of the filter's interpolant at the save,
 // not the stored record -- the two differ by the measurement update.
 template <int d, int q>
-__device__ ODEF_EVENTS_INLINE void event_eval(const EventArgs& P, long i, long k, double tk, double tk1, double t, bool with_cov,
-                                              bool limit, const LaneMem& xl, double (&m)[d * (q + 1)], double& var) {
+__device__ ODEF_FORCE_INLINE void event_eval(const EventArgs& P, long i, long k, double tk, double tk1, double t, bool with_cov,
+                                             bool limit, const LaneMem& xl, double (&m)[d * (q + 1)], double& var) {
   constexpr int NB = q + 1, D = d * NB, TRI = D * (D + 1) / 2;
   const size_t N = (size_t)P.N;
   const int c = P.comp;
@@ -206,10 +200,7 @@ __device__ ODEF_EVENTS_INLINE void event_eval(const EventArgs& P, long i, long k
     for (int a = 0; a < d; ++a)
       if (e == tri(a, a)) dv[a] = v;
   };
-#ifdef __clang__
-  [[clang::always_inline]]
-#endif
-  rts_step_core<d, NB>(P.pc, pij2, mt, B, Cs, msn, sigma2, xl, m, sink);
+  ODEF_INLINE_CALL rts_step_core<d, NB>(P.pc, pij2, mt, B, Cs, msn, sigma2, xl, m, sink);
   var = event_pick<d, 0, d>(dv, c);
 }
 
@@ -222,7 +213,7 @@ __device__ ODEF_EVENTS_INLINE void event_eval(const EventArgs& P, long i, long k
 //   its stored record.  Otherwise the left limit, not the stored mean, is the right end of the secant.  (The smoothed interpolant is
 //   continuous at the saves.)
 template <int d, int q>
-__device__ ODEF_EVENTS_INLINE void event_refine_lane(const EventArgs& P, long i, long slot, const LaneMem& xl) {
+__device__ ODEF_FORCE_INLINE void event_refine_lane(const EventArgs& P, long i, long slot, const LaneMem& xl) {
   constexpr int NB = q + 1, D = d * NB;
   static_assert(d <= kEventMaxD && D <= kEventMaxState, "event location: d <= 4, d (q + 1) <= 12");
   const size_t N = (size_t)P.N, o = (size_t)slot * N + (size_t)i;

@@ -1,6 +1,7 @@
-// Host-side scaffold of the post-processing passes over the records (summary.hip, errors.hip, datalik.hip): scratch buffers that
-// grow, the event pair that times a pass, and the release of device pointers.  Host code only; like summary.h, errors.h and
-// datalik.h this header includes none of the step headers, so that no filter / smoother kernel depends on it.
+// Host-side scaffold of the post-processing passes over the records (summary.hip, errors.hip, datalik.hip, datalik_times.hip,
+// events.hip): scratch buffers that grow, the event pair that times a pass, and the release of device pointers.  Host code only;
+// like summary.h, errors.h, datalik.h and events.h this header includes none of the step headers, so that no filter / smoother
+// kernel depends on it.
 #pragma once
 
 #include <hip/hip_runtime.h>

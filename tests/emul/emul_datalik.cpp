@@ -5,6 +5,7 @@
 // that a sanitiser build sees any access past the records, the observations or the outputs.  Not part of the product.
 #define ODEF_HOST_EMUL 1
 #include "../../odefilters.jl_amd/csrc/datalik_kernels.h"
+#include "../../odefilters.jl_amd/csrc/dispatch_dq.h"
 
 #include <cmath>
 #include <cstring>
@@ -19,23 +20,6 @@ void run_lanes(const DataLikArgs& a) {
   constexpr int D = d * (q + 1), TRI = D * (D + 1) / 2;
   std::vector<double> x(TRI);
   for (long i = 0; i < a.N; ++i) data_loglik_lane<d, q>(a, i, 0, LaneMem{x.data(), 1});
-}
-
-template <int d>
-bool run_order(int q, const DataLikArgs& a) {
-  switch (q) {
-    case 1: run_lanes<d, 1>(a); return true;
-    case 2: run_lanes<d, 2>(a); return true;
-    case 3: run_lanes<d, 3>(a); return true;
-    case 4: run_lanes<d, 4>(a); return true;
-    case 5:
-      if constexpr (d * 6 <= kDataLikMaxState) {
-        run_lanes<d, 5>(a);
-        return true;
-      }
-      return false;
-    default: return false;
-  }
 }
 
 }  // namespace
@@ -96,13 +80,6 @@ extern "C" int emul_datalik(int d, int q, const double* At, const double* Qt, co
   a.per_traj = per_traj;
   a.loglik = loglik;
   a.maha = maha;
-  bool ok = false;
-  switch (d) {
-    case 1: ok = run_order<1>(q, a); break;
-    case 2: ok = run_order<2>(q, a); break;
-    case 3: ok = run_order<3>(q, a); break;
-    case 4: ok = run_order<4>(q, a); break;
-    default: break;
-  }
+  const bool ok = dispatch_dq<kDataLikMaxD, kDataLikMaxState>(d, q, [&]<int dd, int qq>() { run_lanes<dd, qq>(a); });
   return ok ? 0 : -1;
 }

@@ -7,6 +7,7 @@
 // records, the observations or the outputs.  Not part of the product.
 #define ODEF_HOST_EMUL 1
 #include "../../odefilters.jl_amd/csrc/datalik_times_kernels.h"
+#include "../../odefilters.jl_amd/csrc/dispatch_dq.h"
 
 #include <cstring>
 #include <vector>
@@ -16,31 +17,15 @@ using namespace odef;
 namespace {
 
 template <int d, int q>
-bool run_lanes(DataLikTimesArgs a, int wave) {
-  if constexpr (d * (q + 1) <= kDataLikTimesMaxState) {
-    constexpr int D = d * (q + 1), TRI = D * (D + 1) / 2;
-    std::vector<double> x(TRI);
-    for (long i = 0; i < a.N; ++i) {
-      a.host_n_hi = 0;
-      if (wave > 1 && a.adaptive)
-        for (long l = i / wave * wave; l < a.N && l < (i / wave + 1) * wave; ++l)
-          if (a.nsaved[l] > a.host_n_hi) a.host_n_hi = a.nsaved[l];
-      data_loglik_times_lane<d, q>(a, i, 0, true, LaneMem{x.data(), 1});
-    }
-    return true;
-  }
-  return false;
-}
-
-template <int d>
-bool run_order(int q, const DataLikTimesArgs& a, int wave) {
-  switch (q) {
-    case 1: return run_lanes<d, 1>(a, wave);
-    case 2: return run_lanes<d, 2>(a, wave);
-    case 3: return run_lanes<d, 3>(a, wave);
-    case 4: return run_lanes<d, 4>(a, wave);
-    case 5: return run_lanes<d, 5>(a, wave);
-    default: return false;
+void run_lanes(DataLikTimesArgs a, int wave) {
+  constexpr int D = d * (q + 1), TRI = D * (D + 1) / 2;
+  std::vector<double> x(TRI);
+  for (long i = 0; i < a.N; ++i) {
+    a.host_n_hi = 0;
+    if (wave > 1 && a.adaptive)
+      for (long l = i / wave * wave; l < a.N && l < (i / wave + 1) * wave; ++l)
+        if (a.nsaved[l] > a.host_n_hi) a.host_n_hi = a.nsaved[l];
+    data_loglik_times_lane<d, q>(a, i, 0, true, LaneMem{x.data(), 1});
   }
 }
 
@@ -76,11 +61,6 @@ extern "C" int emul_datalik_times(int d, int q, const double* At, const double* 
   a.per_traj = per_traj;
   a.loglik = loglik;
   a.maha = maha;
-  switch (d) {
-    case 1: return run_order<1>(q, a, wave) ? 0 : -1;
-    case 2: return run_order<2>(q, a, wave) ? 0 : -1;
-    case 3: return run_order<3>(q, a, wave) ? 0 : -1;
-    case 4: return run_order<4>(q, a, wave) ? 0 : -1;
-    default: return -1;
-  }
+  const bool ok = dispatch_dq<kDataLikMaxD, kDataLikTimesMaxState>(d, q, [&]<int dd, int qq>() { run_lanes<dd, qq>(a, wave); });
+  return ok ? 0 : -1;
 }

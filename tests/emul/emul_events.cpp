@@ -4,6 +4,7 @@
 // the record count of its group of 64 lanes as the wave-uniform bound, as the kernel does.  Buffers have their exact size, so that a
 // sanitiser build sees any access past the records, the inputs or the outputs.  Not part of the product.
 #define ODEF_HOST_EMUL 1
+#include "../../odefilters.jl_amd/csrc/dispatch_dq.h"
 #include "../../odefilters.jl_amd/csrc/events_kernels.h"
 
 #include <algorithm>
@@ -22,27 +23,6 @@ void refine_lanes(const EventArgs& a) {
     for (long i = 0; i < a.N; ++i) event_refine_lane<d, q>(a, i, s, LaneMem{x.data(), 1});
 }
 
-template <int d>
-bool refine_order(int q, const EventArgs& a) {
-  if (d * (q + 1) > kEventMaxState) return false;
-  switch (q) {
-    case 1: refine_lanes<d, 1>(a); return true;
-    case 2:
-      if constexpr (d * 3 <= kEventMaxState) { refine_lanes<d, 2>(a); return true; }
-      return false;
-    case 3:
-      if constexpr (d * 4 <= kEventMaxState) { refine_lanes<d, 3>(a); return true; }
-      return false;
-    case 4:
-      if constexpr (d * 5 <= kEventMaxState) { refine_lanes<d, 4>(a); return true; }
-      return false;
-    case 5:
-      if constexpr (d * 6 <= kEventMaxState) { refine_lanes<d, 5>(a); return true; }
-      return false;
-    default: return false;
-  }
-}
-
 }  // namespace
 
 // Records mean [n_save][D][N], cov [n_save][TRI][N], diff [n_save][N] and, for source 1, smean / scov; times t [n_save] (fixed grid) or
@@ -52,7 +32,7 @@ extern "C" int emul_events(int d, int q, const double* At, const double* Qt, con
                            const double* diff, const double* smean, const double* scov, const double* t, const int* nsaved, int adaptive,
                            long N, long n_save, int source, int comp, int dir, int K, const double* level, int level_per_traj, int* count,
                            double* time, double* tvar, double* u, int* direction, int* save, int* neval) {
-  if (d < 1 || d > kEventMaxD || q < 1 || q > 5 || d * (q + 1) > kEventMaxState) return -1;
+  if (!has_dq<kEventMaxD, kEventMaxState>(d, q)) return -1;
   EventArgs a;
   std::memset(&a, 0, sizeof a);
   std::memcpy(a.pc.At, At, sizeof a.pc.At);
@@ -92,13 +72,6 @@ extern "C" int emul_events(int d, int q, const double* At, const double* Qt, con
     }
     for (long i = i0; i < i1; ++i) event_scan_lane(a, i, n_hi);
   }
-  bool ok = false;
-  switch (d) {
-    case 1: ok = refine_order<1>(q, a); break;
-    case 2: ok = refine_order<2>(q, a); break;
-    case 3: ok = refine_order<3>(q, a); break;
-    case 4: ok = refine_order<4>(q, a); break;
-    default: break;
-  }
+  const bool ok = dispatch_dq<kEventMaxD, kEventMaxState>(d, q, [&]<int dd, int qq>() { refine_lanes<dd, qq>(a); });
   return ok ? 0 : -1;
 }
