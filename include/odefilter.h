@@ -41,6 +41,8 @@
  *                                   answers in the SciML interface it plugs into, asked of the finished posterior
  *   odef_summary_field ids          nothing in the reference: per-time mean and covariance of the ensemble's Gaussian mixture,
  *                                   reduced on the device and read with odef_get (see odef_summary_field)
+ *   odef_quantile_field ids         nothing in the reference: per-time quantiles of the ensemble's posterior means (median,
+ *                                   credible bands), selected on the device (see odef_quantile_field)
  *   odef_group_* / odef_allgather   nothing in the reference (it has no ensemble and no distributed code):
  *                                   the EnsembleProblem axis sharded over the GPUs of one node by ONE host process, the
  *                                   per-trajectory path above unchanged on every shard, one RCCL all-gather at the end
@@ -144,10 +146,10 @@ typedef enum {
   ODEF_F_COUNT_
 } odef_field;
 
-/* Derived outputs and their caches.  Four families of fields are computed from the records on the device when first asked for --
+/* Derived outputs and their caches.  Five families of fields are computed from the records on the device when first asked for --
  * the ensemble summary (odef_summary_field), the solution errors (odef_errors_field), the data log-likelihood
- * (odef_data_field) and the event times (odef_event_field) -- and cached; odef_field_bytes, odef_get and odef_get_device serve them like any other field.  One rule says
- * when a cached result is dropped, so that the next request computes it again.  The context tracks seven things that can change:
+ * (odef_data_field) the event times (odef_event_field) and the ensemble quantiles (odef_quantile_field) -- and cached; odef_field_bytes, odef_get and odef_get_device serve them like any other field.  One rule says
+ * when a cached result is dropped, so that the next request computes it again.  The context tracks eight things that can change:
  *   the filter records    MEAN, COV_TRIL, DIFFUSION, T                 source 0
  *   the smoothed records  SMOOTH_MEAN, SMOOTH_COV_TRIL                 source 1
  *   the dense records     DENSE_MEAN, DENSE_COV_TRIL                   source 2
@@ -155,17 +157,19 @@ typedef enum {
  *   the bound truth       ODEF_E_REFERENCE
  *   the observations      ODEF_L_OBS_SAVE / COMPONENT / VALUE / NOISE / TIME
  *   the event spec        ODEF_EV_SPEC / ODEF_EV_LEVEL
+ *   the probabilities     ODEF_Q_PROBS
  * and what is derived from what:
  *   the summary of source k       its record set; a new problem drops it as well
  *   the errors of source k        its record set, the bound truth, the problem
  *   the data log-likelihood       the filter records, the observations, the problem
  *   the events of source k        its record set, the filter records (both sources predict from them), the event spec, the problem
+ *   the quantiles of source k     its record set, the problem (as for the summary), the probabilities
  *   the filter records that odef_solve_fixed leaves staged for odef_smooth (the workgroup-per-trajectory path)   the filter records
  * A record set changes when an entry point writes it -- odef_solve_* all three (every summary includes its trajectories by the
  * RETCODE of the solve), odef_smooth the smoothed, odef_dense_output / odef_dense_sample the dense records -- and when the caller
  * may: odef_bind_device of one of its fields replaces the buffer, and odef_get_device of one hands out a WRITABLE pointer, so both
  * count as a change of the whole set.  odef_set_problem* change the problem, a bind of ODEF_E_REFERENCE the truth, a bind of an
- * ODEF_L_OBS_* the observations, a bind of ODEF_EV_SPEC or ODEF_EV_LEVEL the event spec.  odef_get, the host copy, changes nothing.  Records edited through a pointer taken EARLIER are not
+ * ODEF_L_OBS_* the observations, a bind of ODEF_EV_SPEC or ODEF_EV_LEVEL the event spec, a bind of ODEF_Q_PROBS the probabilities.  odef_get, the host copy, changes nothing.  Records edited through a pointer taken EARLIER are not
  * seen: take the pointer again (or bind) after writing. */
 
 /* Ensemble summary per time, reduced on the device (nothing in the reference: it has no ensemble).  For one time and the n
@@ -353,6 +357,39 @@ typedef enum {
   ODEF_EV_LEVEL = 281 /* odef_bind_device only */
 } odef_event_field;
 
+/* Ensemble quantiles per time, selected on the device: the order statistics that the ensemble summary leaves out (SciML's
+ * EnsembleSummary: med, qlow, qhigh; nothing in the reference, it has no ensemble).  For one time s, one component a < d and
+ * probabilities p_1..p_P (1 <= P <= 8, each finite and in [0, 1]; they need not be sorted or distinct), with x_(0) <= ... <=
+ * x_(n-1) the sorted values of row a of the mean over the n trajectories INCLUDED at s by the rule of the summary (RETCODE ==
+ * ODEF_RET_SUCCESS and the d solution entries of the mean at s finite):
+ *   h = (double)(n-1) p,  lo = min(floor(h), n-1),  hi = min(lo+1, n-1),  g = h - lo,
+ *   Q = x_(lo) if g == 0, else x_(lo) + g (x_(hi) - x_(lo))      difference, product and sum rounded once each, no FMA
+ * -- the type-7 rule of Julia's quantile and numpy's default.  With n = 0 every Q is NaN.
+ *   ODEF_Q_FILTER / _SMOOTH / _DENSE              double [n_t][P][d]   source 0 (n_t = odef_n_save) / 1 / 2 (n_t = n_q)
+ *   ODEF_Q_COUNT_FILTER / _SMOOTH / _DENSE        int64  [n_t]         the n used; equals ODEF_S_*_COUNT
+ *   ODEF_Q_PROBS   double [P]   odef_bind_device only: device memory that stays the caller's (read only; copied to the host and
+ *                               validated there; P follows from the byte count); NULL lets it go
+ * Field id = ODEF_Q_BASE + 8 * source + quantity.  odef_field_bytes, odef_get and odef_get_device accept the six output ids
+ * (odef_bind_device does not).  The first request for a source after its records or the probabilities changed runs the pass on
+ * the context's stream -- exact radix selection on order-preserving 64-bit keys, integer counts only, no floating-point atomics:
+ * the result is the order statistic itself and two requests agree bit for bit; the pass synchronises the stream once per slab of
+ * 1024 / d times, to read back how many digit passes the slab needs -- and caches both arrays (dropped as "Derived
+ * outputs and their caches" above says).  Refused with a message: everything the summary refuses (any source before a solve,
+ * source 1 before odef_smooth, source 2 before a dense output, sources 0 / 1 after an ADAPTIVE solve: evaluate odef_dense_output
+ * at common times and use source 2); no probabilities bound; a byte count that is not 8 P with 1 <= P <= 8; a probability that
+ * is NaN or outside [0, 1]; d > 32.  odef_kernel_time_ms / odef_kernel_name report the last pass as which = 6 (its n_launches:
+ * the launches of that pass). */
+typedef enum {
+  ODEF_Q_BASE = 320,
+  ODEF_Q_FILTER = 320,
+  ODEF_Q_COUNT_FILTER = 321,
+  ODEF_Q_SMOOTH = 328,
+  ODEF_Q_COUNT_SMOOTH = 329,
+  ODEF_Q_DENSE = 336,
+  ODEF_Q_COUNT_DENSE = 337,
+  ODEF_Q_PROBS = 344 /* odef_bind_device only */
+} odef_quantile_field;
+
 /* POD mirror of the reference's keyword structs (src/algorithms.jl:23-28,46-51) plus the
  * ensemble shape.  Zero-initialise, set struct_size = sizeof(odef_config). */
 typedef struct {
@@ -486,7 +523,7 @@ int odef_bind_device(odef_ctx* ctx, int field, void* dev_ptr, size_t bytes);
 int odef_synchronize(odef_ctx* ctx);
 
 /* Device time of the last filter (which=0) / smoother (which=1) / ensemble-summary (which=2) / solution-error (which=3) /
- * data-likelihood (which=4) / event-location (which=5) launch, measured with
+ * data-likelihood (which=4) / event-location (which=5) / ensemble-quantile (which=6) launch, measured with
  * hipEvents on the launch stream; n_launches = kernels launched by that call. */
 int odef_kernel_time_ms(odef_ctx* ctx, int which, float* ms, int* n_launches);
 /* Name of the kernel that call launched (the dominant one of a multi-kernel pass), as a profiler prints it, e.g.

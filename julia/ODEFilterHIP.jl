@@ -92,6 +92,16 @@ const EV_SMOOTH_SAVE = 269
 const EV_SMOOTH_NEVAL = 270
 const EV_SPEC = 280
 const EV_LEVEL = 281
+# ensemble quantiles per time (odef_quantile_field, include/odefilter.h): id = Q_BASE + 8 * source + quantity (0 the quantiles,
+# 1 the count), one input that odef_bind_device alone takes.  UNTESTED like the rest of this file.
+const Q_BASE = 320
+const Q_FILTER = 320
+const Q_COUNT_FILTER = 321
+const Q_SMOOTH = 328
+const Q_COUNT_SMOOTH = 329
+const Q_DENSE = 336
+const Q_COUNT_DENSE = 337
+const Q_PROBS = 344
 const RETCODES = (:Success, :MaxIters, :DtLessThanMin, :Unstable, :Unstable)
 
 """Ensemble algorithm: all trajectories of an `EnsembleProblem` on one GPU (`devices` empty / one entry) or sharded
@@ -106,7 +116,7 @@ end
 EnsembleHIP(rhs::Symbol; device=-1, devices=Int32[]) = EnsembleHIP(device, rhs, collect(Int32, devices))
 
 lasterr(ctx) = unsafe_string(ccall((:odef_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx))
-# which kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) / data-likelihood (4) / event-location (5) pass launched, and its device time in ms
+# which kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) / data-likelihood (4) / event-location (5) / ensemble-quantile (6) pass launched, and its device time in ms
 function kernel_name(ctx, which::Integer)
     buf = zeros(UInt8, 256)
     GC.@preserve buf ccall((:odef_kernel_name, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{UInt8}, Csize_t), ctx, which, buf, length(buf))
@@ -142,6 +152,26 @@ function ensemble_summary(ctx, d::Integer; source::Integer=0)
     n_t = Int(nb[] ÷ 8); tri = d * (d + 1) ÷ 2
     return (n = fetch(ctx, id(0), Int64, n_t), mean = fetch(ctx, id(1), Float64, d, n_t),
             within = fetch(ctx, id(2), Float64, tri, n_t), between = fetch(ctx, id(3), Float64, tri, n_t))
+end
+
+"""
+    ensemble_quantiles(ctx, d, probs; source=0) -> (n, q)
+
+Per-time quantiles of the ensemble held by the live context `ctx` (state dimension of the ODE `d`), selected on the device:
+`q[a, p, s]` is the type-7 quantile (Julia's `quantile` default) `p` of solution component `a` of the posterior means over the
+`n[s]` trajectories included at time `s` (Success retcode, finite mean); NaN where `n[s] == 0`.  `probs` is a DEVICE pointer that
+stays the caller's, given as `(ptr, bytes)`: Float64 [P], 1 <= P <= 8, each in [0, 1].  The result is the order statistic
+itself (exact radix selection), interpolated with one rounding per operation.  source 0: filter records, 1: smoothed records,
+2: the last `odef_dense_output` result (the only one an adaptive solve admits).  UNTESTED.
+"""
+function ensemble_quantiles(ctx, d::Integer, probs; source::Integer=0)
+    ptr, bytes = probs
+    check(ccall((:odef_bind_device, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Csize_t), ctx, Q_PROBS, ptr, bytes), ctx)
+    id(q) = Q_BASE + 8 * source + q
+    nb = Ref{Csize_t}(0)
+    check(ccall((:odef_field_bytes, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Csize_t}), ctx, id(1), nb), ctx)
+    n_t = Int(nb[] ÷ 8); P = Int(bytes ÷ 8)
+    return (n = fetch(ctx, id(1), Int64, n_t), q = fetch(ctx, id(0), Float64, d, P, n_t))
 end
 
 """

@@ -21,6 +21,7 @@
 #include "errors.h"
 #include "datalik.h"
 #include "events.h"
+#include "quantiles.h"
 
 using namespace odef;
 
@@ -40,7 +41,7 @@ struct RhsInfo { int d, np; };
 const RhsInfo kRhs[] = {{2, 3}, {3, 3}, {2, 4}, {2, 1}, {2, 2}, {28, 0}, {16, 1}, {2, 3}};
 
 // the passes a context times and names: `which` of odef_kernel_time_ms / odef_kernel_name
-enum Pass { kPassFilter = 0, kPassSmooth = 1, kPassSummary = 2, kPassErrors = 3, kPassDataLik = 4, kPassEvents = 5, kPassCount };
+enum Pass { kPassFilter = 0, kPassSmooth = 1, kPassSummary = 2, kPassErrors = 3, kPassDataLik = 4, kPassEvents = 5, kPassQuantiles = 6, kPassCount };
 
 }  // namespace
 
@@ -90,6 +91,8 @@ struct odef_ctx {
   Buf obs[5];            // ODEF_L_OBS_SAVE / COMPONENT / VALUE / NOISE / TIME: caller memory, read only
   EventsState events;    // cached event times of the filter and smoothed posterior (odef_event_field)
   Buf evin[2];           // ODEF_EV_SPEC / ODEF_EV_LEVEL: caller memory, read only
+  QuantileState quantiles;  // cached ensemble quantiles of the filter, smoothed and dense records (odef_quantile_field)
+  Buf qprobs;            // ODEF_Q_PROBS: caller memory, read only
   // odef_group runs its shards concurrently: with `defer` set, odef_solve_* / odef_smooth return after the launch and
   // complete_pending() does the wait + timing (pending: 1 = filter, 2 = smoother)
   bool defer = false;
@@ -270,6 +273,7 @@ enum : unsigned {
   kTruth = 1u << 4,         // ODEF_E_REFERENCE
   kObservations = 1u << 5,  // ODEF_L_OBS_*
   kEventSpec = 1u << 6,     // ODEF_EV_SPEC, ODEF_EV_LEVEL
+  kQuantileProbs = 1u << 7, // ODEF_Q_PROBS
 };
 
 // the record set an ODEF_F_* id belongs to (0: none)
@@ -295,12 +299,14 @@ void records_changed(odef_ctx* c, unsigned what) {
   if (what & (kFilterRecs | kObservations | kProblem)) c->datalik.valid = false;
   for (int k = 0; k < 2; ++k)  // events of source k: record set k, the filter records (both sources predict from them), spec, problem
     if (what & (kFilterRecs << k | kFilterRecs | kEventSpec | kProblem)) c->events.src[k].valid = false;
+  for (int k = 0; k < 3; ++k)  // quantiles of source k: record set k, the problem (as for the summary), the bound probabilities
+    if (what & (kFilterRecs << k | kProblem | kQuantileProbs)) c->quantiles.src[k].valid = false;
   // The filter records resident in the stage: the filter records.  odef_smooth works in the stage and leaves the smoothed records
   // (or another block layout) there, so new smoothed records end the residency as well.
   if (what & (kFilterRecs | kSmoothRecs)) c->stage_filter_recs = 0;
 }
 
-// One family of derived outputs (odef_summary_field / odef_errors_field / odef_data_field / odef_event_field).  `check` touches no device; `fetch`
+// One family of derived outputs (odef_summary_field / odef_errors_field / odef_data_field / odef_event_field / odef_quantile_field).  `check` touches no device; `fetch`
 // runs after it and returns the cached device array, running the pass first when the cache is stale.
 struct DerivedFamily {
   bool (*owns)(int field);
@@ -318,19 +324,23 @@ bool is_summary_field(int field) {
 // number of times of a summary source
 long summary_times(const odef_ctx* c, int source) { return source == 2 ? c->n_q : c->n_save; }
 
-int summary_check(const odef_ctx* c, int field, const char* who) {
-  const int source = (field - ODEF_S_BASE) / 8;
-  if (!c->solved) return fail(c, "%s: ensemble summary requested before a solve (call odef_solve_* first)", who);
+// what the per-time reductions over the ensemble (summary, quantiles) ask of source 0 / 1 / 2; `what` names the reduction
+int ensemble_source_check(const odef_ctx* c, int source, const char* what, const char* who) {
+  if (!c->solved) return fail(c, "%s: %s requested before a solve (call odef_solve_* first)", who, what);
   if (source == 2) {
     if (!c->f[ODEF_F_DENSE_MEAN].valid || c->n_q < 1)
-      return fail(c, "%s: ensemble summary of source 2 needs odef_dense_output (or odef_dense_sample) first", who);
+      return fail(c, "%s: %s of source 2 needs odef_dense_output (or odef_dense_sample) first", who, what);
     return 0;
   }
   if (c->adaptive)
     return fail(c, "%s: the records of one save index of an adaptive solve lie at different times per trajectory; "
                    "evaluate odef_dense_output at common times and use source 2", who);
-  if (source == 1 && !c->smoothed_done) return fail(c, "%s: ensemble summary of the smoothed records needs odef_smooth first", who);
+  if (source == 1 && !c->smoothed_done) return fail(c, "%s: %s of the smoothed records needs odef_smooth first", who, what);
   return 0;
+}
+
+int summary_check(const odef_ctx* c, int field, const char* who) {
+  return ensemble_source_check(c, (field - ODEF_S_BASE) / 8, "ensemble summary", who);
 }
 
 size_t summary_bytes(const odef_ctx* c, int field) {
@@ -623,11 +633,66 @@ size_t events_bytes(const odef_ctx* c, int field) {
   }
 }
 
+// odef_quantile_field: id = ODEF_Q_BASE + 8 source + quantity (0: the quantiles, 1: the count), and the input that odef_bind_device
+// alone takes
+bool is_quantile_output(int field) {
+  return field >= ODEF_Q_BASE && field < ODEF_Q_BASE + 8 * 3 && (field - ODEF_Q_BASE) % 8 < 2;
+}
+
+int quantiles_check(const odef_ctx* c, int field, const char* who) {
+  if (ensemble_source_check(c, (field - ODEF_Q_BASE) / 8, "ensemble quantiles", who)) return -1;
+  if (c->d > 32) return fail(c, "%s: ensemble quantiles are built for d <= 32 (got d = %d)", who, c->d);
+  if (!c->qprobs.ptr)
+    return fail(c, "%s: ensemble quantiles: no probabilities bound: bind ODEF_Q_PROBS (double [P], 1 <= P <= 8) with odef_bind_device", who);
+  if (c->qprobs.bytes % sizeof(double) != 0 || c->qprobs.bytes < sizeof(double) || c->qprobs.bytes > 8 * sizeof(double))
+    return fail(c, "%s: ensemble quantiles: ODEF_Q_PROBS holds %zu bytes, it is double [P] with 1 <= P <= 8", who, c->qprobs.bytes);
+  return 0;
+}
+
+size_t quantiles_bytes(const odef_ctx* c, int field) {
+  const int source = (field - ODEF_Q_BASE) / 8, quantity = (field - ODEF_Q_BASE) % 8;
+  const size_t P = c->qprobs.bytes / sizeof(double);
+  return (size_t)summary_times(c, source) * 8 * (quantity == 1 ? 1 : P * (size_t)c->d);
+}
+
+// the cached array of a quantile field; the first request after the source's records or the probabilities changed runs the pass
+int quantiles_fetch(odef_ctx* c, int field, const char* who, void** ptr) {
+  const int source = (field - ODEF_Q_BASE) / 8, quantity = (field - ODEF_Q_BASE) % 8;
+  const long n_t = summary_times(c, source);
+  const int P = (int)(c->qprobs.bytes / sizeof(double));
+  QuantileCache& qc = c->quantiles.src[source];
+  if (!qc.valid || qc.n_t != n_t || qc.P != P) {
+    static const int kMean[3] = {ODEF_F_MEAN, ODEF_F_SMOOTH_MEAN, ODEF_F_DENSE_MEAN};
+    QuantileArgs a{};
+    a.mean = (const double*)c->f[kMean[source]].ptr;
+    a.retcode = (const int*)c->f[ODEF_F_RETCODE].ptr;
+    a.N = c->cfg.n_traj;
+    a.n_t = n_t;
+    a.d = c->d;
+    a.D = c->D;
+    a.P = P;
+    if (!a.mean || !a.retcode) return fail(c, "%s: the records of quantile source %d hold no data", who, source);
+    // the probabilities are copied to the host and validated there
+    HIPCHK(c, hipMemcpyAsync(a.probs, c->qprobs.ptr, sizeof(double) * P, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int p = 0; p < P; ++p)
+      if (!(a.probs[p] >= 0.0 && a.probs[p] <= 1.0))
+        return fail(c, "%s: ensemble quantiles: probability %d of ODEF_Q_PROBS is %g, outside [0, 1]", who, p, a.probs[p]);
+    std::string err;
+    if (quantiles_run(c->quantiles, qc, a, c->stream, &c->ms[kPassQuantiles], &c->nl[kPassQuantiles], err))
+      return fail(c, "%s: %s", who, err.c_str());
+    std::snprintf(c->kname[kPassQuantiles], sizeof c->kname[kPassQuantiles], "odef::quantile_hist_kernel");
+  }
+  *ptr = quantity == 1 ? (void*)qc.count : (void*)qc.q;
+  return 0;
+}
+
 const DerivedFamily kDerived[] = {
     {is_summary_field, summary_check, summary_bytes, summary_fetch},
     {is_errors_field, errors_check, errors_bytes, errors_fetch},
     {is_datalik_output, datalik_check, datalik_bytes, datalik_fetch},
     {is_event_output, events_check, events_bytes, events_fetch, true},
+    {is_quantile_output, quantiles_check, quantiles_bytes, quantiles_fetch},
 };
 
 // the family that owns a field id, or nullptr: an ODEF_F_* buffer, a bind-only id, or no id at all
@@ -854,6 +919,7 @@ void odef_destroy(odef_ctx* c) {
   errors_free(c->errors);
   datalik_free(c->datalik);
   events_free(c->events);
+  quantiles_free(c->quantiles);
   for (int k = 0; k < 4; ++k)
     if (c->ev[k]) (void)hipEventDestroy(c->ev[k]);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1430,6 +1496,16 @@ int odef_bind_device(odef_ctx* c, int field, void* dev_ptr, size_t bytes) {
       b.bound = true;
     }
     records_changed(c, kEventSpec);
+    return 0;
+  }
+  if (field == ODEF_Q_PROBS) {  // the probabilities of the ensemble quantiles: caller memory, read only; NULL lets it go
+    c->qprobs = Buf{};
+    if (dev_ptr) {
+      c->qprobs.ptr = dev_ptr;
+      c->qprobs.bytes = bytes;
+      c->qprobs.bound = true;
+    }
+    records_changed(c, kQuantileProbs);
     return 0;
   }
   if (field < 0 || field >= ODEF_F_COUNT_ || field == ODEF_F_U0) return fail(c, "odef_bind_device: field %d cannot be bound", field);

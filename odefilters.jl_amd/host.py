@@ -128,6 +128,32 @@ def event_field(source: int, quantity: int) -> int:
 def _is_event_field(f: int) -> bool:
     return EV_BASE <= f < EV_BASE + 16 and (f - EV_BASE) % 8 < 7
 
+
+# ensemble quantiles per time (odef_quantile_field, include/odefilter.h): id = Q_BASE + 8 * source + quantity
+Q_BASE = 320
+Q_QUANTILES, Q_COUNT = 0, 1
+Q_PROBS = 344  # odef_bind_device only: the probabilities double [P] in device memory
+QUANTILE_FIELDS = {
+    "ODEF_Q_BASE": 320,
+    "ODEF_Q_FILTER": 320, "ODEF_Q_COUNT_FILTER": 321,
+    "ODEF_Q_SMOOTH": 328, "ODEF_Q_COUNT_SMOOTH": 329,
+    "ODEF_Q_DENSE": 336, "ODEF_Q_COUNT_DENSE": 337,
+    "ODEF_Q_PROBS": 344,
+}
+K_QUANTILES = 6  # `which` of odef_kernel_time_ms / odef_kernel_name
+
+
+def quantile_field(source: int, quantity: int) -> int:
+    """Field id of an ensemble-quantile array: source 0 filter / 1 smoothed / 2 dense records, quantity 0 the quantiles
+    [n_t, P, d] / 1 the count [n_t]."""
+    if source not in (0, 1, 2) or quantity not in (0, 1):
+        raise OdefError(f"no ensemble-quantile field for source {source}, quantity {quantity}")
+    return Q_BASE + 8 * source + quantity
+
+
+def _is_quantile_field(f: int) -> bool:
+    return Q_BASE <= f < Q_BASE + 24 and (f - Q_BASE) % 8 < 2
+
 # dtype and shape (of a Context `c`) of every derived field, by family and quantity; the source does not matter
 _FLAT = lambda c: (-1,)  # noqa: E731  ([n_t] counts, [N] per-trajectory values)
 _DERIVED_LAYOUT = {
@@ -150,6 +176,10 @@ _DERIVED = {S_BASE + 8 * s + q: _DERIVED_LAYOUT["summary", q] for s in range(3) 
 _DERIVED.update({E_BASE + 8 * s + q: _DERIVED_LAYOUT["errors", q] for s in range(2) for q in range(6)})
 _DERIVED.update({L_BASE + q: _DERIVED_LAYOUT["data", q] for q in range(2)})
 _DERIVED.update({EV_BASE + 8 * s + q: _DERIVED_LAYOUT["event", q] for s in range(2) for q in range(7)})
+# quantiles [n_t, P, d]: P is that of the bound probabilities, so it follows from the flat size and the source's count [n_t]
+_DERIVED.update({Q_BASE + 8 * s + Q_QUANTILES: (np.float64, lambda c, s=s: (c.field_bytes(Q_BASE + 8 * s + Q_COUNT) // 8, -1, c.d))
+                 for s in range(3)})
+_DERIVED.update({Q_BASE + 8 * s + Q_COUNT: (np.int64, _FLAT) for s in range(3)})
 
 
 def _fetch(lib, h, f: int, dtype=None) -> np.ndarray:
@@ -561,6 +591,11 @@ class DeviceGroup:
         n, m, w, b = self.ensemble_moments(S_SOURCE_SMOOTH if smoothed else S_SOURCE_FILTER)
         return EnsembleSummary.from_moments(_fetch(self.lib, self.lib.odef_group_ctx(self._h, 0), F_T), n, m, w, b)
 
+    def ensemble_quantiles(self, source: int, probs=None):
+        """Refused: the quantiles of the shards do not pool (exact pooling would all-reduce the per-pass histograms)."""
+        raise OdefError("ensemble_quantiles of a sharded ensemble: the quantiles of the shards do not pool into those of the "
+                        "whole ensemble; solve the ensemble on one device (Context.ensemble_quantiles)")
+
     def shard_kernel_ms(self, which=0):
         ms = []
         for g in range(self.G):
@@ -741,6 +776,27 @@ class Context:
         lower triangles.  The first request after the records changed launches the reduction; later ones read the cache."""
         return tuple(self.get(summary_field(source, qty)) for qty in range(4))
 
+    def bind_quantile_probs(self, ptr: int, P: int):
+        """The probabilities of `ensemble_quantiles`: double [P] in device memory that stays the caller's (read only),
+        1 <= P <= 8, each in [0, 1]; they need not be sorted or distinct.  ptr = 0 lets them go."""
+        self._quantile_probs = None  # what is bound now is the caller's
+        self._chk(self.lib.odef_bind_device(self._h, Q_PROBS, _vp(ptr) if ptr else None, int(P) * 8))
+
+    def ensemble_quantiles(self, source: int, probs=None):
+        """Type-7 quantiles (numpy's default, Julia's `quantile`) of every solution component of the posterior means over the
+        included trajectories, per time of the filter (0), smoothed (1) or last dense-output (2) records, selected on the device
+        (`odef_quantile_field`): (count [n_t] int64, q [n_t, P, d]).  `probs`: uploaded and bound first, unless they are bit for bit
+        those this method bound last (a bind drops the cache); None: those bound already.  Exact: q is the order statistic itself, interpolated with one rounding per operation.  The
+        first request after the records or the probabilities changed launches the pass; later ones read the cache."""
+        if probs is not None:
+            p = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, float)).reshape(-1))
+            if getattr(self, "_quantile_probs", None) != p.tobytes():
+                # device memory owned by torch, kept alive by the context
+                self._quantile_bufs = _to_device((p,), self.cfg.device) if p.size else None
+                self.bind_quantile_probs(self._quantile_bufs[0].data_ptr() if p.size else 0, p.size)
+                self._quantile_probs = p.tobytes() if p.size else None
+        return self.get(quantile_field(source, Q_COUNT)), self.get(quantile_field(source, Q_QUANTILES))
+
     @staticmethod
     def _solution_errors(lib, h, source: int):
         return {key: _fetch(lib, h, errors_field(source, qty))
@@ -833,7 +889,7 @@ class Context:
 
     def kernel_name(self, which=0) -> str:
         """Name of the kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) / data-likelihood
-        (4) / event-location (5) pass launched, as a profiler prints it."""
+        (4) / event-location (5) / ensemble-quantile (6) pass launched, as a profiler prints it."""
         buf = C.create_string_buffer(256)
         self._chk(self.lib.odef_kernel_name(self._h, which, buf, 256))
         return buf.value.decode()
@@ -1092,6 +1148,11 @@ class EnsembleSummary:
     mean: np.ndarray         # [n_t, d]
     cov_within: np.ndarray   # [n_t, d, d]
     cov_between: np.ndarray  # [n_t, d, d]
+    # the order statistics of the posterior means, with `sol.summary(quantiles=(lo, hi))` (SciML's EnsembleSummary names)
+    med: Optional[np.ndarray] = None             # [n_t, d]
+    qlow: Optional[np.ndarray] = None            # [n_t, d]
+    qhigh: Optional[np.ndarray] = None           # [n_t, d]
+    quantile_probs: Optional[tuple] = None       # (lo, hi)
 
     @classmethod
     def from_moments(cls, t, n, mean, within, between):
@@ -1305,12 +1366,43 @@ class EnsembleSolution:
         self._event_bufs = _to_device(arrays, self.ctx.cfg.device)  # device memory owned by torch, kept alive by the solution
         return Context._events(self.ctx.lib, self.ctx._h, self.ctx, int(sm), self._event_bufs)
 
-    def summary(self, t=None, smoothed: Optional[bool] = None) -> EnsembleSummary:
+    def _no_sharded_quantiles(self):
+        if self.shard is not None and self.shard[3] > 1:
+            raise OdefError("quantiles of a sharded ensemble: the quantiles of the shards do not pool into those of the whole "
+                            "ensemble (exact pooling would all-reduce the per-pass histograms, which is not built); "
+                            "solve the ensemble on one device, or gather the means")
+
+    def _quantile_source(self, t, smoothed):
+        """Evaluates the dense output when t is given; returns (times, source) by the rules of `summary()`."""
+        sm = self.smoothed if smoothed is None else bool(smoothed)
+        if t is None:
+            if self.adaptive:
+                raise OdefError("quantiles(): an adaptive solve keeps its records at different times per trajectory; "
+                                "pass common times t (the quantiles of the dense output are taken)")
+            return self.t, (S_SOURCE_SMOOTH if sm else S_SOURCE_FILTER)
+        tt = np.ascontiguousarray(np.atleast_1d(np.asarray(t, float)))
+        self.ctx._chk(self.ctx.lib.odef_dense_output(self.ctx._h, _as_dp(tt), len(tt), int(sm)))
+        return tt, S_SOURCE_DENSE
+
+    def quantiles(self, probs, t=None, smoothed: Optional[bool] = None) -> np.ndarray:
+        """[n_t, P, d]: the quantiles `probs` (1 to 8 values in [0, 1]) of every solution component of the posterior means over
+        the ensemble, per time, selected on the device (`odef_quantile_field`) -- the median and the credible bands that
+        `mean +- std` cannot give for a skewed or bimodal ensemble.  Type-7 rule (numpy's default), exact.  t, smoothed and
+        adaptive solves: the rules of `summary()`.  Trajectories are included as in `summary()`; a time without any gives NaN.
+        The quantiles of a sharded ensemble are refused."""
+        self._no_sharded_quantiles()
+        _, source = self._quantile_source(t, smoothed)
+        return self.ctx.ensemble_quantiles(source, probs)[1]
+
+    def summary(self, t=None, smoothed: Optional[bool] = None, quantiles=None) -> EnsembleSummary:
         """Mean path of the ensemble and its uncertainty, reduced on the device (`odef_summary_field`): nothing but the four
         small arrays crosses to the host.  t = None: the save grid of a fixed-grid solve, smoothed when the solution is (the rule
         of `sol.u`).  With t: the dense output `sol(t)` is evaluated on the device and summarised.  Adaptive solves need t (their
         records of one save index lie at different times per trajectory).  A distributed solve returns the summary of the WHOLE
-        ensemble on every rank: one all_gather of the per-shard blocks, pooled with `merge_moments`."""
+        ensemble on every rank: one all_gather of the per-shard blocks, pooled with `merge_moments`.  quantiles=(lo, hi): the
+        summary also carries `qlow`, `med`, `qhigh` [n_t, d] (`quantiles()` with (lo, 0.5, hi), one pass); not for sharded solves."""
+        if quantiles is not None:
+            self._no_sharded_quantiles()
         sm = self.smoothed if smoothed is None else bool(smoothed)
         if t is None:
             if self.adaptive:
@@ -1326,7 +1418,13 @@ class EnsembleSolution:
             from . import dist as od
 
             moments = merge_moments(od.allgather_moments(moments, self.shard[3]))
-        return EnsembleSummary.from_moments(tt, *moments)
+        out = EnsembleSummary.from_moments(tt, *moments)
+        if quantiles is not None:  # the dense records of `t` are still those just summarised
+            lo, hi = (float(v) for v in quantiles)
+            q = self.ctx.ensemble_quantiles(S_SOURCE_DENSE if t is not None else S_SOURCE_SMOOTH if sm else S_SOURCE_FILTER,
+                                            (lo, 0.5, hi))[1]
+            out.qlow, out.med, out.qhigh, out.quantile_probs = q[:, 0], q[:, 1], q[:, 2], (lo, hi)
+        return out
 
     def sample_states(self, n: int = 1, seed: int = 0x5A3B1E, noise_scale: float = 1.0) -> np.ndarray:
         """`sample_states(sol, n)` (src/solution_sampling.jl:15-18, 24-62): [N, n_save, D, n] joint draws of the
