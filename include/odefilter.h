@@ -43,6 +43,8 @@
  *                                   reduced on the device and read with odef_get (see odef_summary_field)
  *   odef_quantile_field ids         nothing in the reference: per-time quantiles of the ensemble's posterior means (median,
  *                                   credible bands), selected on the device (see odef_quantile_field)
+ *   odef_wsummary_field ids         nothing in the reference: the summary with a weight per trajectory -- what the ensemble
+ *                                   predicts given data --, the effective sample size and the log evidence (see odef_wsummary_field)
  *   odef_group_* / odef_allgather   nothing in the reference (it has no ensemble and no distributed code):
  *                                   the EnsembleProblem axis sharded over the GPUs of one node by ONE host process, the
  *                                   per-trajectory path above unchanged on every shard, one RCCL all-gather at the end
@@ -146,10 +148,10 @@ typedef enum {
   ODEF_F_COUNT_
 } odef_field;
 
-/* Derived outputs and their caches.  Five families of fields are computed from the records on the device when first asked for --
+/* Derived outputs and their caches.  Six families of fields are computed from the records on the device when first asked for --
  * the ensemble summary (odef_summary_field), the solution errors (odef_errors_field), the data log-likelihood
- * (odef_data_field) the event times (odef_event_field) and the ensemble quantiles (odef_quantile_field) -- and cached; odef_field_bytes, odef_get and odef_get_device serve them like any other field.  One rule says
- * when a cached result is dropped, so that the next request computes it again.  The context tracks eight things that can change:
+ * (odef_data_field) the event times (odef_event_field), the ensemble quantiles (odef_quantile_field) and the weighted ensemble summary (odef_wsummary_field) -- and cached; odef_field_bytes, odef_get and odef_get_device serve them like any other field.  One rule says
+ * when a cached result is dropped, so that the next request computes it again.  The context tracks nine things that can change:
  *   the filter records    MEAN, COV_TRIL, DIFFUSION, T                 source 0
  *   the smoothed records  SMOOTH_MEAN, SMOOTH_COV_TRIL                 source 1
  *   the dense records     DENSE_MEAN, DENSE_COV_TRIL                   source 2
@@ -158,18 +160,20 @@ typedef enum {
  *   the observations      ODEF_L_OBS_SAVE / COMPONENT / VALUE / NOISE / TIME
  *   the event spec        ODEF_EV_SPEC / ODEF_EV_LEVEL
  *   the probabilities     ODEF_Q_PROBS
+ *   the log-weights       ODEF_W_LOGWEIGHT
  * and what is derived from what:
  *   the summary of source k       its record set; a new problem drops it as well
  *   the errors of source k        its record set, the bound truth, the problem
  *   the data log-likelihood       the filter records, the observations, the problem
  *   the events of source k        its record set, the filter records (both sources predict from them), the event spec, the problem
  *   the quantiles of source k     its record set, the problem (as for the summary), the probabilities
+ *   the weighted summary of source k   its record set, the problem (as for the summary), the log-weights
  *   the filter records that odef_solve_fixed leaves staged for odef_smooth (the workgroup-per-trajectory path)   the filter records
  * A record set changes when an entry point writes it -- odef_solve_* all three (every summary includes its trajectories by the
  * RETCODE of the solve), odef_smooth the smoothed, odef_dense_output / odef_dense_sample the dense records -- and when the caller
  * may: odef_bind_device of one of its fields replaces the buffer, and odef_get_device of one hands out a WRITABLE pointer, so both
  * count as a change of the whole set.  odef_set_problem* change the problem, a bind of ODEF_E_REFERENCE the truth, a bind of an
- * ODEF_L_OBS_* the observations, a bind of ODEF_EV_SPEC or ODEF_EV_LEVEL the event spec, a bind of ODEF_Q_PROBS the probabilities.  odef_get, the host copy, changes nothing.  Records edited through a pointer taken EARLIER are not
+ * ODEF_L_OBS_* the observations, a bind of ODEF_EV_SPEC or ODEF_EV_LEVEL the event spec, a bind of ODEF_Q_PROBS the probabilities, a bind of ODEF_W_LOGWEIGHT the log-weights.  odef_get, the host copy, changes nothing.  Records edited through a pointer taken EARLIER are not
  * seen: take the pointer again (or bind) after writing. */
 
 /* Ensemble summary per time, reduced on the device (nothing in the reference: it has no ensemble).  For one time and the n
@@ -390,6 +394,60 @@ typedef enum {
   ODEF_Q_PROBS = 344 /* odef_bind_device only */
 } odef_quantile_field;
 
+/* Weighted ensemble summary per time, reduced on the device: the ensemble summary with a weight per trajectory -- the
+ * importance-weighted mixture that answers "what does the ensemble predict given the data" when the weights are
+ * exp(data log-likelihood + log prior) -- with the effective sample size and the log evidence (nothing in the reference: it
+ * has no ensemble).
+ *   ODEF_W_LOGWEIGHT   double [N]   odef_bind_device only: the unnormalised log-weights l_i in device memory that stays the
+ *                                   caller's (read only, never written; NULL lets it go; a byte count other than 8 N is
+ *                                   refused).  They are not copied to the host and not validated there: a value that is not
+ *                                   finite (NaN, +-inf: what ODEF_L_DATA_LOGLIK holds for a trajectory it could not score)
+ *                                   EXCLUDES its trajectory.
+ * Independent of the time: L = max l_i over the trajectories with RETCODE == ODEF_RET_SUCCESS and l_i finite; v_i = exp(l_i - L)
+ * for those and 0 for every other.  If no trajectory qualifies, every time has n = 0.  Trajectory i is INCLUDED at time s when
+ * the rule of the summary holds (RETCODE == ODEF_RET_SUCCESS and the d solution entries of the mean at s finite) and l_i is
+ * finite.  With Z = sum v_i over the included, w_i = v_i / Z, and mu_i, Sigma_i as for the summary:
+ *   COUNT         n, the included trajectories (one whose v_i underflowed to 0 still counts)   int64  [n_t]
+ *   MEAN          m = sum_i w_i mu_i                                                           double [n_t][d]
+ *   COV_WITHIN    W = sum_i w_i Sigma_i                                                        double [n_t][d(d+1)/2] packed as for the summary
+ *   COV_BETWEEN   B = sum_i w_i (mu_i - m)(mu_i - m)'                                          double [n_t][d(d+1)/2]
+ *   LOG_EVIDENCE  L + log Z - log n = log((1/n) sum_i exp l_i): with trajectories drawn from the prior and l the data
+ *                 log-likelihood, the Monte-Carlo log marginal likelihood                      double [n_t]
+ *   ESS           Z^2 / sum_i v_i^2, the effective sample size, in [1, n]                      double [n_t]
+ * With n = 0 the three moments, ESS and LOG_EVIDENCE are NaN.  With n > 0 but Z == 0 -- the trajectory that carries L is not
+ * included at s and every other weight underflowed -- plain IEEE arithmetic gives NaN moments, NaN ESS and LOG_EVIDENCE = -inf;
+ * this is not special-cased.  Field id = ODEF_W_BASE + 8 * source + quantity, quantity 0..5 in the order above, sources as for
+ * the summary.  odef_field_bytes, odef_get and odef_get_device accept the eighteen output ids (odef_bind_device does not).  The
+ * first request for a source after its records or the log-weights changed runs the pass on the context's stream -- the shift
+ * and the weights once per request (one exp per trajectory), then the two passes of the summary, the covariance of the means
+ * centred with the final m before it is squared; deterministic, no floating-point atomics: two requests agree bit for bit --
+ * and caches the six arrays (dropped as "Derived outputs and their caches" above says).  Refused with a message: everything
+ * the summary refuses (any source before a solve, source 1 before odef_smooth, source 2 before a dense output, sources 0 / 1
+ * after an ADAPTIVE solve: evaluate odef_dense_output at common times and use source 2); no log-weights bound; d > 32.
+ * odef_kernel_time_ms / odef_kernel_name report the last pass as which = 7. */
+typedef enum {
+  ODEF_W_BASE = 384,
+  ODEF_W_FILTER_COUNT = 384,
+  ODEF_W_FILTER_MEAN = 385,
+  ODEF_W_FILTER_COV_WITHIN = 386,
+  ODEF_W_FILTER_COV_BETWEEN = 387,
+  ODEF_W_FILTER_LOG_EVIDENCE = 388,
+  ODEF_W_FILTER_ESS = 389,
+  ODEF_W_SMOOTH_COUNT = 392,
+  ODEF_W_SMOOTH_MEAN = 393,
+  ODEF_W_SMOOTH_COV_WITHIN = 394,
+  ODEF_W_SMOOTH_COV_BETWEEN = 395,
+  ODEF_W_SMOOTH_LOG_EVIDENCE = 396,
+  ODEF_W_SMOOTH_ESS = 397,
+  ODEF_W_DENSE_COUNT = 400,
+  ODEF_W_DENSE_MEAN = 401,
+  ODEF_W_DENSE_COV_WITHIN = 402,
+  ODEF_W_DENSE_COV_BETWEEN = 403,
+  ODEF_W_DENSE_LOG_EVIDENCE = 404,
+  ODEF_W_DENSE_ESS = 405,
+  ODEF_W_LOGWEIGHT = 408 /* odef_bind_device only */
+} odef_wsummary_field;
+
 /* POD mirror of the reference's keyword structs (src/algorithms.jl:23-28,46-51) plus the
  * ensemble shape.  Zero-initialise, set struct_size = sizeof(odef_config). */
 typedef struct {
@@ -523,7 +581,7 @@ int odef_bind_device(odef_ctx* ctx, int field, void* dev_ptr, size_t bytes);
 int odef_synchronize(odef_ctx* ctx);
 
 /* Device time of the last filter (which=0) / smoother (which=1) / ensemble-summary (which=2) / solution-error (which=3) /
- * data-likelihood (which=4) / event-location (which=5) / ensemble-quantile (which=6) launch, measured with
+ * data-likelihood (which=4) / event-location (which=5) / ensemble-quantile (which=6) / weighted-summary (which=7) launch, measured with
  * hipEvents on the launch stream; n_launches = kernels launched by that call. */
 int odef_kernel_time_ms(odef_ctx* ctx, int which, float* ms, int* n_launches);
 /* Name of the kernel that call launched (the dominant one of a multi-kernel pass), as a profiler prints it, e.g.

@@ -102,6 +102,29 @@ const Q_COUNT_SMOOTH = 329
 const Q_DENSE = 336
 const Q_COUNT_DENSE = 337
 const Q_PROBS = 344
+# weighted ensemble summary per time (odef_wsummary_field, include/odefilter.h): id = W_BASE + 8 * source + quantity (0 COUNT,
+# 1 MEAN, 2 COV_WITHIN, 3 COV_BETWEEN, 4 LOG_EVIDENCE, 5 ESS), one input that odef_bind_device alone takes.  UNTESTED like the
+# rest of this file.
+const W_BASE = 384
+const W_FILTER_COUNT = 384
+const W_FILTER_MEAN = 385
+const W_FILTER_COV_WITHIN = 386
+const W_FILTER_COV_BETWEEN = 387
+const W_FILTER_LOG_EVIDENCE = 388
+const W_FILTER_ESS = 389
+const W_SMOOTH_COUNT = 392
+const W_SMOOTH_MEAN = 393
+const W_SMOOTH_COV_WITHIN = 394
+const W_SMOOTH_COV_BETWEEN = 395
+const W_SMOOTH_LOG_EVIDENCE = 396
+const W_SMOOTH_ESS = 397
+const W_DENSE_COUNT = 400
+const W_DENSE_MEAN = 401
+const W_DENSE_COV_WITHIN = 402
+const W_DENSE_COV_BETWEEN = 403
+const W_DENSE_LOG_EVIDENCE = 404
+const W_DENSE_ESS = 405
+const W_LOGWEIGHT = 408
 const RETCODES = (:Success, :MaxIters, :DtLessThanMin, :Unstable, :Unstable)
 
 """Ensemble algorithm: all trajectories of an `EnsembleProblem` on one GPU (`devices` empty / one entry) or sharded
@@ -116,7 +139,7 @@ end
 EnsembleHIP(rhs::Symbol; device=-1, devices=Int32[]) = EnsembleHIP(device, rhs, collect(Int32, devices))
 
 lasterr(ctx) = unsafe_string(ccall((:odef_last_error, LIB), Cstring, (Ptr{Cvoid},), ctx))
-# which kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) / data-likelihood (4) / event-location (5) / ensemble-quantile (6) pass launched, and its device time in ms
+# which kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) / data-likelihood (4) / event-location (5) / ensemble-quantile (6) / weighted-summary (7) pass launched, and its device time in ms
 function kernel_name(ctx, which::Integer)
     buf = zeros(UInt8, 256)
     GC.@preserve buf ccall((:odef_kernel_name, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{UInt8}, Csize_t), ctx, which, buf, length(buf))
@@ -172,6 +195,27 @@ function ensemble_quantiles(ctx, d::Integer, probs; source::Integer=0)
     check(ccall((:odef_field_bytes, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Csize_t}), ctx, id(1), nb), ctx)
     n_t = Int(nb[] ÷ 8); P = Int(bytes ÷ 8)
     return (n = fetch(ctx, id(1), Int64, n_t), q = fetch(ctx, id(0), Float64, d, P, n_t))
+end
+
+"""
+    weighted_ensemble_summary(ctx, d, log_weights; source=0) -> (n, mean, within, between, log_evidence, ess)
+
+Per-time summary of the ensemble held by the live context `ctx` (state dimension of the ODE `d`) with a weight per trajectory,
+reduced on the device: the moments of the mixture with weights proportional to `exp(l_i)`, the log evidence
+`log((1/n) sum exp l_i)` and the effective sample size.  `log_weights` is a DEVICE pointer that stays the caller's, given as
+`(ptr, bytes)`: Float64 [N]; a value that is not finite excludes its trajectory.  source 0: filter records, 1: smoothed records,
+2: the last `odef_dense_output` result (the only one an adaptive solve admits).  UNTESTED.
+"""
+function weighted_ensemble_summary(ctx, d::Integer, log_weights; source::Integer=0)
+    ptr, bytes = log_weights
+    check(ccall((:odef_bind_device, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Csize_t), ctx, W_LOGWEIGHT, ptr, bytes), ctx)
+    id(q) = W_BASE + 8 * source + q
+    nb = Ref{Csize_t}(0)
+    check(ccall((:odef_field_bytes, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Csize_t}), ctx, id(0), nb), ctx)
+    n_t = Int(nb[] ÷ 8); tri = d * (d + 1) ÷ 2
+    return (n = fetch(ctx, id(0), Int64, n_t), mean = fetch(ctx, id(1), Float64, d, n_t),
+            within = fetch(ctx, id(2), Float64, tri, n_t), between = fetch(ctx, id(3), Float64, tri, n_t),
+            log_evidence = fetch(ctx, id(4), Float64, n_t), ess = fetch(ctx, id(5), Float64, n_t))
 end
 
 """

@@ -8,7 +8,7 @@ smooth of ProbNumDiffEq.jl) behind a C ABI.  Holds only what that path needs:
 from . import _build
 from .host import (  # noqa: F401
     EK0, EK1, IEKS, Context, EnsembleHIP, EnsembleProblem, EnsembleSolution, EnsembleSummary, Events, ODEProblem, OdefController, OdefError,
-    compile_rhs, fixed_time_grid, ibm, load_library, merge_moments, preconditioner, predict, shard_ensemble, smooth_step, solve, solve_ieks, unpack_tril, update,
+    compile_rhs, fixed_time_grid, ibm, load_library, merge_moments, merge_weighted_moments, preconditioner, predict, shard_ensemble, smooth_step, solve, solve_ieks, unpack_tril, update,
 )
 
 build = _build.build

@@ -22,6 +22,7 @@
 #include "datalik.h"
 #include "events.h"
 #include "quantiles.h"
+#include "wsummary.h"
 
 using namespace odef;
 
@@ -41,7 +42,7 @@ struct RhsInfo { int d, np; };
 const RhsInfo kRhs[] = {{2, 3}, {3, 3}, {2, 4}, {2, 1}, {2, 2}, {28, 0}, {16, 1}, {2, 3}};
 
 // the passes a context times and names: `which` of odef_kernel_time_ms / odef_kernel_name
-enum Pass { kPassFilter = 0, kPassSmooth = 1, kPassSummary = 2, kPassErrors = 3, kPassDataLik = 4, kPassEvents = 5, kPassQuantiles = 6, kPassCount };
+enum Pass { kPassFilter = 0, kPassSmooth = 1, kPassSummary = 2, kPassErrors = 3, kPassDataLik = 4, kPassEvents = 5, kPassQuantiles = 6, kPassWSummary = 7, kPassCount };
 
 }  // namespace
 
@@ -93,6 +94,8 @@ struct odef_ctx {
   Buf evin[2];           // ODEF_EV_SPEC / ODEF_EV_LEVEL: caller memory, read only
   QuantileState quantiles;  // cached ensemble quantiles of the filter, smoothed and dense records (odef_quantile_field)
   Buf qprobs;            // ODEF_Q_PROBS: caller memory, read only
+  WSummaryState wsummary;  // cached weighted ensemble summaries of the filter, smoothed and dense records (odef_wsummary_field)
+  Buf wlogw;             // ODEF_W_LOGWEIGHT: caller memory, read only
   // odef_group runs its shards concurrently: with `defer` set, odef_solve_* / odef_smooth return after the launch and
   // complete_pending() does the wait + timing (pending: 1 = filter, 2 = smoother)
   bool defer = false;
@@ -274,6 +277,7 @@ enum : unsigned {
   kObservations = 1u << 5,  // ODEF_L_OBS_*
   kEventSpec = 1u << 6,     // ODEF_EV_SPEC, ODEF_EV_LEVEL
   kQuantileProbs = 1u << 7, // ODEF_Q_PROBS
+  kLogWeights = 1u << 8,    // ODEF_W_LOGWEIGHT
 };
 
 // the record set an ODEF_F_* id belongs to (0: none)
@@ -301,12 +305,14 @@ void records_changed(odef_ctx* c, unsigned what) {
     if (what & (kFilterRecs << k | kFilterRecs | kEventSpec | kProblem)) c->events.src[k].valid = false;
   for (int k = 0; k < 3; ++k)  // quantiles of source k: record set k, the problem (as for the summary), the bound probabilities
     if (what & (kFilterRecs << k | kProblem | kQuantileProbs)) c->quantiles.src[k].valid = false;
+  for (int k = 0; k < 3; ++k)  // weighted summary of source k: record set k, the problem (as for the summary), the bound log-weights
+    if (what & (kFilterRecs << k | kProblem | kLogWeights)) c->wsummary.src[k].valid = false;
   // The filter records resident in the stage: the filter records.  odef_smooth works in the stage and leaves the smoothed records
   // (or another block layout) there, so new smoothed records end the residency as well.
   if (what & (kFilterRecs | kSmoothRecs)) c->stage_filter_recs = 0;
 }
 
-// One family of derived outputs (odef_summary_field / odef_errors_field / odef_data_field / odef_event_field / odef_quantile_field).  `check` touches no device; `fetch`
+// One family of derived outputs (odef_summary_field / odef_errors_field / odef_data_field / odef_event_field / odef_quantile_field / odef_wsummary_field).  `check` touches no device; `fetch`
 // runs after it and returns the cached device array, running the pass first when the cache is stale.
 struct DerivedFamily {
   bool (*owns)(int field);
@@ -324,7 +330,7 @@ bool is_summary_field(int field) {
 // number of times of a summary source
 long summary_times(const odef_ctx* c, int source) { return source == 2 ? c->n_q : c->n_save; }
 
-// what the per-time reductions over the ensemble (summary, quantiles) ask of source 0 / 1 / 2; `what` names the reduction
+// what the per-time reductions over the ensemble (summary, quantiles, weighted summary) ask of source 0 / 1 / 2; `what` names the reduction
 int ensemble_source_check(const odef_ctx* c, int source, const char* what, const char* who) {
   if (!c->solved) return fail(c, "%s: %s requested before a solve (call odef_solve_* first)", who, what);
   if (source == 2) {
@@ -687,12 +693,64 @@ int quantiles_fetch(odef_ctx* c, int field, const char* who, void** ptr) {
   return 0;
 }
 
+// odef_wsummary_field: id = ODEF_W_BASE + 8 source + quantity (0..5 as in the header's table), and the input that odef_bind_device
+// alone takes
+bool is_wsummary_output(int field) {
+  return field >= ODEF_W_BASE && field < ODEF_W_BASE + 8 * 3 && (field - ODEF_W_BASE) % 8 < 6;
+}
+
+int wsummary_check(const odef_ctx* c, int field, const char* who) {
+  if (ensemble_source_check(c, (field - ODEF_W_BASE) / 8, "weighted ensemble summary", who)) return -1;
+  if (c->d > 32) return fail(c, "%s: the weighted ensemble summary is built for d <= 32 (got d = %d)", who, c->d);
+  if (!c->wlogw.ptr)
+    return fail(c, "%s: weighted ensemble summary: no weights bound: bind ODEF_W_LOGWEIGHT (double [N]) with odef_bind_device", who);
+  return 0;
+}
+
+size_t wsummary_bytes(const odef_ctx* c, int field) {
+  const int source = (field - ODEF_W_BASE) / 8, quantity = (field - ODEF_W_BASE) % 8;
+  const size_t tri = (size_t)c->d * (c->d + 1) / 2;
+  const size_t per_time[6] = {1, (size_t)c->d, tri, tri, 1, 1};
+  return (size_t)summary_times(c, source) * 8 * per_time[quantity];
+}
+
+// the cached array of a weighted-summary field; the first request after the source's records or the weights changed runs the pass
+int wsummary_fetch(odef_ctx* c, int field, const char* who, void** ptr) {
+  const int source = (field - ODEF_W_BASE) / 8, quantity = (field - ODEF_W_BASE) % 8;
+  const long n_t = summary_times(c, source);
+  WSummaryCache& wc = c->wsummary.src[source];
+  if (!wc.valid || wc.n_t != n_t) {
+    static const int kMean[3] = {ODEF_F_MEAN, ODEF_F_SMOOTH_MEAN, ODEF_F_DENSE_MEAN};
+    static const int kCov[3] = {ODEF_F_COV_TRIL, ODEF_F_SMOOTH_COV_TRIL, ODEF_F_DENSE_COV_TRIL};
+    WSummaryArgs a;
+    a.mean = (const double*)c->f[kMean[source]].ptr;
+    a.cov = (const double*)c->f[kCov[source]].ptr;
+    a.retcode = (const int*)c->f[ODEF_F_RETCODE].ptr;
+    a.logw = (const double*)c->wlogw.ptr;
+    a.N = c->cfg.n_traj;
+    a.n_t = n_t;
+    a.d = c->d;
+    a.D = c->D;
+    a.TRI = c->TRI;
+    if (!a.mean || !a.cov || !a.retcode) return fail(c, "%s: the records of summary source %d hold no data", who, source);
+    std::string err;
+    int walk = 0;
+    if (wsummary_run(c->wsummary, wc, a, c->stream, &c->ms[kPassWSummary], &c->nl[kPassWSummary], &walk, err))
+      return fail(c, "%s: %s", who, err.c_str());
+    std::snprintf(c->kname[kPassWSummary], sizeof c->kname[kPassWSummary], "odef::wsummary_sums_kernel<%d>", walk);
+  }
+  void* const p[6] = {wc.count, wc.mean, wc.within, wc.between, wc.logev, wc.ess};
+  *ptr = p[quantity];
+  return 0;
+}
+
 const DerivedFamily kDerived[] = {
     {is_summary_field, summary_check, summary_bytes, summary_fetch},
     {is_errors_field, errors_check, errors_bytes, errors_fetch},
     {is_datalik_output, datalik_check, datalik_bytes, datalik_fetch},
     {is_event_output, events_check, events_bytes, events_fetch, true},
     {is_quantile_output, quantiles_check, quantiles_bytes, quantiles_fetch},
+    {is_wsummary_output, wsummary_check, wsummary_bytes, wsummary_fetch},
 };
 
 // the family that owns a field id, or nullptr: an ODEF_F_* buffer, a bind-only id, or no id at all
@@ -920,6 +978,7 @@ void odef_destroy(odef_ctx* c) {
   datalik_free(c->datalik);
   events_free(c->events);
   quantiles_free(c->quantiles);
+  wsummary_free(c->wsummary);
   for (int k = 0; k < 4; ++k)
     if (c->ev[k]) (void)hipEventDestroy(c->ev[k]);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -1506,6 +1565,19 @@ int odef_bind_device(odef_ctx* c, int field, void* dev_ptr, size_t bytes) {
       c->qprobs.bound = true;
     }
     records_changed(c, kQuantileProbs);
+    return 0;
+  }
+  if (field == ODEF_W_LOGWEIGHT) {  // the log-weights of the weighted summary: caller memory, read only; NULL lets it go
+    if (dev_ptr && bytes != sizeof(double) * (size_t)c->cfg.n_traj)
+      return fail(c, "odef_bind_device: ODEF_W_LOGWEIGHT is double [N]: %zu bytes for N = %ld, got %zu",
+                  sizeof(double) * (size_t)c->cfg.n_traj, (long)c->cfg.n_traj, bytes);
+    c->wlogw = Buf{};
+    if (dev_ptr) {
+      c->wlogw.ptr = dev_ptr;
+      c->wlogw.bytes = bytes;
+      c->wlogw.bound = true;
+    }
+    records_changed(c, kLogWeights);
     return 0;
   }
   if (field < 0 || field >= ODEF_F_COUNT_ || field == ODEF_F_U0) return fail(c, "odef_bind_device: field %d cannot be bound", field);

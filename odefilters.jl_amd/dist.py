@@ -65,3 +65,21 @@ def allgather_moments(moments, world: int):
     dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
     g = allgather_shards(torch.from_numpy(np.ascontiguousarray(flat)).to(dev), world).cpu().numpy()
     return [(g[r, :, 0].astype(np.int64), g[r, :, 1:1 + d], g[r, :, 1 + d:1 + d + tri], g[r, :, 1 + d + tri:]) for r in range(world)]
+
+
+def allgather_weighted_moments(moments, world: int):
+    """`allgather_moments` for a rank's weighted-summary block (count, mean, within, between, log_evidence, ess): the list of
+    every rank's six arrays, in rank order, for `host.merge_weighted_moments`."""
+    import numpy as np
+
+    n, m, w, b, le, ess = moments
+    if world == 1:
+        return [moments]
+    n_t, d, tri = m.shape[0], m.shape[1], w.shape[1]
+    flat = np.concatenate([np.asarray(n, float).reshape(n_t, 1), m, w, b, np.asarray(le, float).reshape(n_t, 1),
+                           np.asarray(ess, float).reshape(n_t, 1)], axis=1)  # [n_t, 3 + d + 2 tri]
+    dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else torch.device("cpu")
+    g = allgather_shards(torch.from_numpy(np.ascontiguousarray(flat)).to(dev), world).cpu().numpy()
+    o = 1 + d + 2 * tri
+    return [(g[r, :, 0].astype(np.int64), g[r, :, 1:1 + d], g[r, :, 1 + d:1 + d + tri], g[r, :, 1 + d + tri:o], g[r, :, o], g[r, :, o + 1])
+            for r in range(world)]

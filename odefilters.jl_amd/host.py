@@ -154,6 +154,29 @@ def quantile_field(source: int, quantity: int) -> int:
 def _is_quantile_field(f: int) -> bool:
     return Q_BASE <= f < Q_BASE + 24 and (f - Q_BASE) % 8 < 2
 
+
+# weighted ensemble summary per time (odef_wsummary_field, include/odefilter.h): id = W_BASE + 8 * source + quantity
+W_BASE = 384
+W_COUNT, W_MEAN, W_COV_WITHIN, W_COV_BETWEEN, W_LOG_EVIDENCE, W_ESS = range(6)
+W_LOGWEIGHT = 408  # odef_bind_device only: the unnormalised log-weights double [N] in device memory
+_W_QUANTITIES = ("COUNT", "MEAN", "COV_WITHIN", "COV_BETWEEN", "LOG_EVIDENCE", "ESS")
+WSUMMARY_FIELDS = {"ODEF_W_BASE": 384, "ODEF_W_LOGWEIGHT": 408}
+WSUMMARY_FIELDS.update({f"ODEF_W_{src}_{name}": 384 + 8 * s + q
+                        for s, src in enumerate(("FILTER", "SMOOTH", "DENSE")) for q, name in enumerate(_W_QUANTITIES)})
+K_WSUMMARY = 7  # `which` of odef_kernel_time_ms / odef_kernel_name
+
+
+def wsummary_field(source: int, quantity: int) -> int:
+    """Field id of a weighted-summary array: source 0 filter / 1 smoothed / 2 dense records, quantity 0 COUNT / 1 MEAN /
+    2 COV_WITHIN / 3 COV_BETWEEN / 4 LOG_EVIDENCE / 5 ESS."""
+    if source not in (0, 1, 2) or quantity not in range(6):
+        raise OdefError(f"no weighted-summary field for source {source}, quantity {quantity}")
+    return W_BASE + 8 * source + quantity
+
+
+def _is_wsummary_field(f: int) -> bool:
+    return W_BASE <= f < W_BASE + 24 and (f - W_BASE) % 8 < 6
+
 # dtype and shape (of a Context `c`) of every derived field, by family and quantity; the source does not matter
 _FLAT = lambda c: (-1,)  # noqa: E731  ([n_t] counts, [N] per-trajectory values)
 _DERIVED_LAYOUT = {
@@ -180,6 +203,9 @@ _DERIVED.update({EV_BASE + 8 * s + q: _DERIVED_LAYOUT["event", q] for s in range
 _DERIVED.update({Q_BASE + 8 * s + Q_QUANTILES: (np.float64, lambda c, s=s: (c.field_bytes(Q_BASE + 8 * s + Q_COUNT) // 8, -1, c.d))
                  for s in range(3)})
 _DERIVED.update({Q_BASE + 8 * s + Q_COUNT: (np.int64, _FLAT) for s in range(3)})
+# weighted summary: the four arrays of the summary, then LOG_EVIDENCE and ESS [n_t]
+_DERIVED.update({W_BASE + 8 * s + q: _DERIVED_LAYOUT["summary", q] for s in range(3) for q in range(4)})
+_DERIVED.update({W_BASE + 8 * s + q: (np.float64, _FLAT) for s in range(3) for q in (W_LOG_EVIDENCE, W_ESS)})
 
 
 def _fetch(lib, h, f: int, dtype=None) -> np.ndarray:
@@ -591,6 +617,31 @@ class DeviceGroup:
         n, m, w, b = self.ensemble_moments(S_SOURCE_SMOOTH if smoothed else S_SOURCE_FILTER)
         return EnsembleSummary.from_moments(_fetch(self.lib, self.lib.odef_group_ctx(self._h, 0), F_T), n, m, w, b)
 
+    def weighted_moments(self, source: int, log_weights):
+        """Weighted ensemble summary of the WHOLE ensemble (`Context.weighted_moments`): `log_weights` [N] is split by
+        `odef_group_shard`, every shard binds its block and reduces its own records on its device (`odef_wsummary_field`), the
+        per-shard blocks (kilobytes) are pooled on the host with `merge_weighted_moments`.  Returns (count, mean, within, between,
+        log_evidence, ess)."""
+        w = np.ascontiguousarray(np.asarray(log_weights, float).reshape(-1))
+        if w.size != self.N:
+            raise OdefError(f"log_weights: {w.size} values for {self.N} trajectories")
+        # Every shard is bound to its new block before the old blocks are let go (no context is left pointing at freed
+        # memory if an upload or a bind raises), and only then are the passes run.
+        bufs = [_to_device((w[lo:lo + count],), self._devices[g])[0] for g, (lo, count) in enumerate(map(self.shard, range(self.G)))]
+        old = getattr(self, "_log_weight_bufs", None)
+        self._log_weight_bufs = [old, bufs]  # device memory owned by torch, kept alive by the group
+        for g, buf in enumerate(bufs):
+            c = self.lib.odef_group_ctx(self._h, g)
+            if self.lib.odef_bind_device(c, W_LOGWEIGHT, _vp(buf.data_ptr()), buf.numel() * 8) != 0:
+                raise OdefError(self.lib.odef_last_error(c).decode())
+        self._log_weight_bufs = bufs
+        parts = []
+        for g in range(self.G):
+            c = self.lib.odef_group_ctx(self._h, g)
+            parts.append(tuple(_fetch(self.lib, c, f).reshape(_DERIVED[f][1](self))
+                               for f in (wsummary_field(source, qty) for qty in range(6))))
+        return merge_weighted_moments(parts)
+
     def ensemble_quantiles(self, source: int, probs=None):
         """Refused: the quantiles of the shards do not pool (exact pooling would all-reduce the per-pass histograms)."""
         raise OdefError("ensemble_quantiles of a sharded ensemble: the quantiles of the shards do not pool into those of the "
@@ -797,6 +848,62 @@ class Context:
                 self._quantile_probs = p.tobytes() if p.size else None
         return self.get(quantile_field(source, Q_COUNT)), self.get(quantile_field(source, Q_QUANTILES))
 
+    def bind_log_weights(self, ptr: int, N: int):
+        """The unnormalised log-weights of `weighted_moments`: double [N] in device memory that stays the caller's (read only,
+        never written); N is the context's number of trajectories.  A value that is not finite excludes its trajectory.  ptr = 0
+        lets them go."""
+        self._log_weights = None  # what is bound now is the caller's
+        self._chk(self.lib.odef_bind_device(self._h, W_LOGWEIGHT, _vp(ptr) if ptr else None, int(N) * 8))
+
+    def _bind_log_weight_tensor(self, tensor, key):
+        """Binds a float64 [N] torch tensor on the context's device and keeps it alive; `key`: its bytes when they are known on
+        the host (a later request with the same bytes binds nothing), else None."""
+        if tensor.numel() != self.N:
+            raise OdefError(f"log_weights: {tensor.numel()} values for {self.N} trajectories")
+        self._log_weight_buf = tensor
+        self.bind_log_weights(tensor.data_ptr(), self.N)
+        self._log_weights = key
+
+    def weighted_moments(self, source: int, log_weights=None):
+        """Weighted ensemble summary per time of the filter (0), smoothed (1) or last dense-output (2) records, reduced on the
+        device (`odef_wsummary_field`): (count [n_t] int64, mean [n_t, d], within [n_t, tri], between [n_t, tri], log_evidence
+        [n_t], ess [n_t]) of the mixture with weights proportional to exp(log_weights).  `log_weights` [N] (a numpy array, or a
+        torch tensor on any device, which is copied to the host for the comparison -- 8 N bytes -- and uploaded like an array; weights
+        that must not leave the device are bound with `bind_log_weights`): uploaded and bound first, unless they are bit for bit those this method bound last (a bind drops the
+        cache); None: those bound already.  The first request after the records or the weights changed launches the pass; later
+        ones read the cache."""
+        if log_weights is not None:
+            if hasattr(log_weights, "detach"):  # a torch tensor
+                log_weights = log_weights.detach().cpu().numpy()
+            w = np.ascontiguousarray(np.asarray(log_weights, float).reshape(-1))
+            if w.size != self.N:
+                raise OdefError(f"log_weights: {w.size} values for {self.N} trajectories")
+            if getattr(self, "_log_weights", None) != w.tobytes():
+                # device memory owned by torch, kept alive by the context
+                self._bind_log_weight_tensor(_to_device((w,), self.cfg.device)[0], w.tobytes())
+        return tuple(self.get(wsummary_field(source, qty)) for qty in range(6))
+
+    def bind_data_loglik_as_weights(self, log_prior=None):
+        """Binds log-weights = the data log-likelihood of the bound observations (`ODEF_L_DATA_LOGLIK`, computed if need be)
+        + `log_prior` [N] if given, without a trip through the host: a device-to-device COPY into a tensor the context owns
+        (the likelihood's own cache is freed when it is dropped, so its pointer is never bound)."""
+        import torch
+
+        ptr, nbytes = self.device_ptr(L_DATA_LOGLIK)
+
+        class Raw:
+            __cuda_array_interface__ = {"shape": (nbytes // 8,), "typestr": "<f8", "data": (ptr, False), "version": 2}
+
+        dev = torch.device("cuda", int(self.cfg.device) if self.cfg.device >= 0 else torch.cuda.current_device())
+        w = torch.as_tensor(Raw(), device=dev).clone()
+        if log_prior is not None:
+            lp = np.ascontiguousarray(np.asarray(log_prior, float).reshape(-1))
+            if lp.size != self.N:
+                raise OdefError(f"log_prior: {lp.size} values for {self.N} trajectories")
+            w += torch.from_numpy(lp).to(dev)
+        torch.cuda.synchronize(dev)
+        self._bind_log_weight_tensor(w, None)
+
     @staticmethod
     def _solution_errors(lib, h, source: int):
         return {key: _fetch(lib, h, errors_field(source, qty))
@@ -889,7 +996,7 @@ class Context:
 
     def kernel_name(self, which=0) -> str:
         """Name of the kernel the last filter (0) / smoother (1) / ensemble-summary (2) / solution-error (3) / data-likelihood
-        (4) / event-location (5) / ensemble-quantile (6) pass launched, as a profiler prints it."""
+        (4) / event-location (5) / ensemble-quantile (6) / weighted-summary (7) pass launched, as a profiler prints it."""
         buf = C.create_string_buffer(256)
         self._chk(self.lib.odef_kernel_name(self._h, which, buf, 256))
         return buf.value.decode()
@@ -1138,6 +1245,46 @@ def merge_moments(parts):
     return n, np.where(empty, np.nan, mean), np.where(empty, np.nan, within), np.where(empty, np.nan, between)
 
 
+def merge_weighted_moments(parts):
+    """Pooled combination of per-shard weighted ensemble summaries.  parts: iterable of (n [n_t], mean [n_t, d], within [n_t, tri],
+    between [n_t, tri], log_evidence [n_t], ess [n_t]), every shard with its own shift L_r.  The absolute mass of shard r at a
+    time is n_r exp(log_evidence_r) = sum_i exp(l_i); the masses are combined by log-sum-exp, omega_r = mass_r / sum mass, and
+    the moments pool as in `merge_moments` with omega_r in place of n_r / n.  sum v^2 of a shard is recovered as mass_r^2 / ess_r,
+    so ESS = 1 / sum_r omega_r^2 / ess_r; log_evidence = log sum mass - log n with n = sum n_r.  A shard without mass at a time (n_r
+    = 0, or every weight underflowed) is skipped there; with n = 0 everything is NaN, with n > 0 and no mass the moments and ESS are
+    NaN and log_evidence is -inf, as on one device.  Pure numpy."""
+    parts = [(np.asarray(p[0], np.int64),) + tuple(np.asarray(a, float) for a in p[1:]) for p in parts]
+    if not parts:
+        raise OdefError("merge_weighted_moments: no parts")
+    for p in parts:
+        if len(p) != 6:
+            raise OdefError("merge_weighted_moments: a part is (count, mean, within, between, log_evidence, ess)")
+    n_t, d = parts[0][1].shape
+    il = np.tril_indices(d)
+    n = sum(p[0] for p in parts)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        logm = [np.where(p[0] > 0, np.log(np.maximum(p[0], 1).astype(float)) + p[4], -np.inf) for p in parts]  # log mass_r
+        top = np.max(logm, axis=0)
+        has_mass = np.isfinite(top)
+        shift = np.where(has_mass, top, 0.0)
+        rel = [np.where(np.isfinite(a), np.exp(a - shift), 0.0) for a in logm]
+        total = sum(rel)
+        omega = [np.where(has_mass, r / np.where(has_mass, total, 1.0), 0.0) for r in rel]
+        log_evidence = np.where(has_mass, shift + np.log(np.where(has_mass, total, 1.0)), -np.inf) - np.log(n.astype(float))
+        inv_ess = sum(np.where(o > 0, o * o / np.where(o > 0, p[5], 1.0), 0.0) for p, o in zip(parts, omega))
+        ess = 1.0 / inv_ess
+    live = [(o > 0)[:, None] for o in omega]
+    mean = sum(np.where(l, o[:, None] * p[1], 0.0) for p, o, l in zip(parts, omega, live))
+    within = sum(np.where(l, o[:, None] * p[2], 0.0) for p, o, l in zip(parts, omega, live))
+    between = np.zeros_like(within)
+    for p, o, l in zip(parts, omega, live):
+        dm = np.where(l, p[1] - mean, 0.0)
+        between += np.where(l, o[:, None] * (p[3] + dm[:, il[0]] * dm[:, il[1]]), 0.0)
+    dead = ~has_mass
+    nan = lambda a: np.where(dead[:, None], np.nan, a)  # noqa: E731
+    return (n, nan(mean), nan(within), nan(between), np.where(n == 0, np.nan, log_evidence), np.where(dead, np.nan, ess))
+
+
 @dataclass
 class EnsembleSummary:
     """Per-time summary of an ensemble: the equal-weight mixture of the trajectories' Gaussian posteriors has mean `mean` and
@@ -1153,11 +1300,16 @@ class EnsembleSummary:
     qlow: Optional[np.ndarray] = None            # [n_t, d]
     qhigh: Optional[np.ndarray] = None           # [n_t, d]
     quantile_probs: Optional[tuple] = None       # (lo, hi)
+    # with `sol.summary(log_weights=...)` / `sol.posterior_predictive(...)`: the mixture is weighted by w_i proportional to
+    # exp(log_weights_i) instead of 1 / n, and these two say how far to trust it
+    ess: Optional[np.ndarray] = None             # [n_t] effective sample size (sum w)^2 / sum w^2, in [1, n]
+    log_evidence: Optional[np.ndarray] = None    # [n_t] log((1/n) sum_i exp log_weights_i)
 
     @classmethod
-    def from_moments(cls, t, n, mean, within, between):
+    def from_moments(cls, t, n, mean, within, between, log_evidence=None, ess=None):
         d = mean.shape[1]
-        return cls(np.asarray(t, float).reshape(-1), n, mean, unpack_tril(within, d), unpack_tril(between, d))
+        return cls(np.asarray(t, float).reshape(-1), n, mean, unpack_tril(within, d), unpack_tril(between, d),
+                   ess=ess, log_evidence=log_evidence)
 
     @property
     def cov(self) -> np.ndarray:
@@ -1372,13 +1524,13 @@ class EnsembleSolution:
                             "ensemble (exact pooling would all-reduce the per-pass histograms, which is not built); "
                             "solve the ensemble on one device, or gather the means")
 
-    def _quantile_source(self, t, smoothed):
+    def _quantile_source(self, t, smoothed, who="quantiles()", taken="the quantiles of the dense output are taken"):
         """Evaluates the dense output when t is given; returns (times, source) by the rules of `summary()`."""
         sm = self.smoothed if smoothed is None else bool(smoothed)
         if t is None:
             if self.adaptive:
-                raise OdefError("quantiles(): an adaptive solve keeps its records at different times per trajectory; "
-                                "pass common times t (the quantiles of the dense output are taken)")
+                raise OdefError(f"{who}: an adaptive solve keeps its records at different times per trajectory; "
+                                f"pass common times t ({taken})")
             return self.t, (S_SOURCE_SMOOTH if sm else S_SOURCE_FILTER)
         tt = np.ascontiguousarray(np.atleast_1d(np.asarray(t, float)))
         self.ctx._chk(self.ctx.lib.odef_dense_output(self.ctx._h, _as_dp(tt), len(tt), int(sm)))
@@ -1394,13 +1546,19 @@ class EnsembleSolution:
         _, source = self._quantile_source(t, smoothed)
         return self.ctx.ensemble_quantiles(source, probs)[1]
 
-    def summary(self, t=None, smoothed: Optional[bool] = None, quantiles=None) -> EnsembleSummary:
+    def summary(self, t=None, smoothed: Optional[bool] = None, quantiles=None, log_weights=None) -> EnsembleSummary:
         """Mean path of the ensemble and its uncertainty, reduced on the device (`odef_summary_field`): nothing but the four
         small arrays crosses to the host.  t = None: the save grid of a fixed-grid solve, smoothed when the solution is (the rule
         of `sol.u`).  With t: the dense output `sol(t)` is evaluated on the device and summarised.  Adaptive solves need t (their
         records of one save index lie at different times per trajectory).  A distributed solve returns the summary of the WHOLE
         ensemble on every rank: one all_gather of the per-shard blocks, pooled with `merge_moments`.  quantiles=(lo, hi): the
-        summary also carries `qlow`, `med`, `qhigh` [n_t, d] (`quantiles()` with (lo, 0.5, hi), one pass); not for sharded solves."""
+        summary also carries `qlow`, `med`, `qhigh` [n_t, d] (`quantiles()` with (lo, 0.5, hi), one pass); not for sharded solves.
+        log_weights [N] (this rank's trajectories; a distributed solve also takes the whole ensemble's and cuts its block): the
+        mixture is weighted by w_i proportional to exp(log_weights_i) (`odef_wsummary_field`; a value that is not finite excludes
+        its trajectory) and the summary carries `ess` and `log_evidence`; the shards of a distributed solve pool with
+        `merge_weighted_moments`.  Not together with quantiles."""
+        if log_weights is not None:
+            return self._weighted_summary(t, smoothed, quantiles, log_weights)
         if quantiles is not None:
             self._no_sharded_quantiles()
         sm = self.smoothed if smoothed is None else bool(smoothed)
@@ -1425,6 +1583,42 @@ class EnsembleSolution:
                                             (lo, 0.5, hi))[1]
             out.qlow, out.med, out.qhigh, out.quantile_probs = q[:, 0], q[:, 1], q[:, 2], (lo, hi)
         return out
+
+    _BOUND_WEIGHTS = object()  # `_weighted_summary`: the log-weights the context holds already
+
+    def _weighted_summary(self, t, smoothed, quantiles, log_weights) -> EnsembleSummary:
+        if quantiles is not None:
+            raise OdefError("summary(quantiles=..., log_weights=...): weighted quantiles are not built (they would need integer "
+                            "fixed-point weights in the radix histograms to stay exact); ask for one of the two")
+        sharded = self.shard is not None and self.shard[3] > 1
+        if log_weights is not self._BOUND_WEIGHTS:
+            if hasattr(log_weights, "detach"):  # a torch tensor: cut to the rank's block like an array
+                log_weights = log_weights.detach().cpu().numpy()
+            log_weights = np.asarray(log_weights, float).reshape(-1)
+            if sharded and log_weights.size == self.shard[2] != self.ctx.N:
+                log_weights = log_weights[self.shard[0]:self.shard[1]]
+        tt, source = self._quantile_source(t, smoothed, "summary()", "the dense output is summarised")  # (the rules of `summary()`, and its dense output)
+        moments = self.ctx.weighted_moments(source, None if log_weights is self._BOUND_WEIGHTS else log_weights)
+        if sharded:
+            from . import dist as od
+
+            moments = merge_weighted_moments(od.allgather_weighted_moments(moments, self.shard[3]))
+        return EnsembleSummary.from_moments(tt, *moments)
+
+    def posterior_predictive(self, times, data, noise_var, components=None, log_prior=None, t=None,
+                             smoothed: Optional[bool] = None) -> EnsembleSummary:
+        """What the ensemble predicts given noisy measurements: `data_loglik(times, data, noise_var, components)` per
+        trajectory, plus `log_prior` [N] if given, as the log-weights of `summary(t, smoothed, log_weights=...)`.  The weights
+        stay on the device (a device-to-device copy of the likelihood into a tensor the context owns).  With candidates drawn
+        from the prior, `log_evidence` is the Monte-Carlo log marginal likelihood of the data and `ess` says how many candidates
+        still carry weight.  A trajectory the likelihood could not score (NaN) is left out."""
+        self.data_loglik(times, data, noise_var, components)
+        if log_prior is not None and self.shard is not None and self.shard[3] > 1:
+            log_prior = np.asarray(log_prior, float).reshape(-1)
+            if log_prior.size == self.shard[2] != self.ctx.N:
+                log_prior = log_prior[self.shard[0]:self.shard[1]]
+        self.ctx.bind_data_loglik_as_weights(log_prior)
+        return self._weighted_summary(t, smoothed, None, self._BOUND_WEIGHTS)
 
     def sample_states(self, n: int = 1, seed: int = 0x5A3B1E, noise_scale: float = 1.0) -> np.ndarray:
         """`sample_states(sol, n)` (src/solution_sampling.jl:15-18, 24-62): [N, n_save, D, n] joint draws of the
